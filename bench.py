@@ -9,7 +9,7 @@ resident in HBM before the timed region; value = reactors integrated by all rank
 wall time.  PCIe transfers are excluded from `value`; the PCIe-inclusive rate of the same launch is
 reported beside it (`pcie_inclusive`).
 
-Secondary lines in the same JSON object (each sharded over the ranks, max-over-ranks timing):
+Secondary lines in the same JSON object, with --full (each sharded over the ranks, max-over-ranks timing):
   c1   configs[0]: ONE GRI-3.0 CONP reactor (CH4/air phi 1, 1200 K, 1 atm, TIFP, 1e-10/1e-8) through the
        drop-in GivenPressureBatchReactor_EnergyConservation.run(): per-call wall latency (median of 7),
        solver counts, the oracle on one core; plus the reference's serial 20-condition loop
@@ -30,7 +30,18 @@ over the kernel time measured with HIP events on the launch stream) and, on rank
 CPU baseline: the oracle C restatement (OpenMP) timed on a bounded sample of the same workload on
 this host.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--lines c1,c3,c4,c5,rop,lu,rop161,ropext,pfr,hcci]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                       [--full [--lines c1,c3,c4,c5,rop,lu,rop161,ropext,pfr,hcci]]
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the optional
+output dump and the result line (with the headline's solver counts and roofline, which come from the
+timed steps themselves).  Everything that takes runs of its own -- the PCIe-inclusive launch, every
+CPU baseline and every secondary line above -- runs only with --full; without it those keys of the
+result line are null.
+
+--dump-outputs DIR writes what the last timed step returned (tau, T, P, V, Y, stats, t_stop of this
+rank's shard, as a caller of reactor_run receives them) to DIR/<name>.npy in float64.  The inputs are
+a fixed grid, so two builds run with the same arguments can be compared output for output.
 
 Launch: under torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK set) every process is one
 rank.  Run directly with --gpus N > 1, bench.py is its own launcher: it starts N child processes
@@ -216,6 +227,27 @@ def timed(world, fn, steps):
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     return tmax.item(), kern_ms, res
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, res):
+    """--dump-outputs: the result of the last timed step (the dict reactor_run returns), one
+    DIR/<name>.npy per array in float64 (the int32 solver counts are exact in it).  Every array has one
+    row per reactor; a result above DUMP_MAX_BYTES is cut to a fixed, seeded sample of the reactors (the
+    same rows of every array, in ascending order, listed in DIR/rows.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in res.items()
+            if not k.startswith("_") and torch.is_tensor(v)}
+    n = len(next(iter(arrs.values())))
+    row_bytes = sum(a.nbytes // max(n, 1) for a in arrs.values()) + 8
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).permutation(n)[: DUMP_MAX_BYTES // row_bytes])
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
 
 
 def solver_summary(stats):
@@ -633,7 +665,8 @@ def main():
     ap.add_argument("--reactors", type=int, default=0, help="override the headline reactors per GPU (0 = full 65,536)")
     ap.add_argument("--sub-reactors", type=int, default=0, help="cap the c4 / c5 shards (0 = full sweeps)")
     ap.add_argument("--lines", default="c1,c3,c4,c5,rop,lu,rop161,ropext,pfr,hcci",
-                    help="comma list of: c1, c3 (headline, always run), c4, c5, rop, lu, rop161, ropext, pfr, hcci")
+                    help="with --full, comma list of: c1, c3 (headline, always run), c4, c5, rop, lu, rop161, ropext, "
+                         "pfr, hcci")
     ap.add_argument("--rop-states", type=int, default=10_000_000)
     ap.add_argument("--lu-systems", type=int, default=16384)
     ap.add_argument("--big-states", type=int, default=1_000_000)
@@ -641,8 +674,12 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget of the headline")
     ap.add_argument("--cpu-seconds-secondary", type=float, default=6.0, help="CPU-baseline budget of c4 / c5")
     ap.add_argument("--plan", action="store_true", help="print the shard layout / timing protocol (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the PCIe-inclusive launch, the CPU baselines and the secondary lines (--lines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0's shard) to DIR/<name>.npy")
     args = ap.parse_args()
-    lines = set(args.lines.split(","))
+    lines = set(args.lines.split(",")) if args.full else set()  # secondary lines: --full only
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:  # be the launcher (no GPU touched yet)
         visible = None if args.plan else torch.cuda.device_count()
@@ -682,22 +719,26 @@ def main():
     tau = res["tau"].cpu().numpy()
     kern_s = float(np.mean(kern_ms)) / 1e3
     value = n * world * args.steps / tmax
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # PCIe-inclusive rate (reported beside value, never as value): host numpy inputs -> H2D ->
     # one launch -> D2H of tau, T, P, V, Y, stats, on this rank
-    torch.cuda.synchronize()
-    tp = time.perf_counter()
-    rp = dm.reactor_run(cfg, prob, T0, P0, np.ones(n), Y0)
-    host_out = {k: v.cpu().numpy() for k, v in rp.items() if not k.startswith("_")}
-    torch.cuda.synchronize()
-    pcie_s = time.perf_counter() - tp
-    pcie = {"reactors_per_s": n / pcie_s, "seconds": pcie_s, "vs_value": (n / pcie_s) / (value / world),
-            "bytes_h2d": int(T0.nbytes + P0.nbytes + Y0.nbytes + prob.nbytes + 8 * n),
-            "bytes_d2h": int(sum(a.nbytes for a in host_out.values()))}
-    del rp, host_out
+    pcie = None
+    if args.full:
+        torch.cuda.synchronize()
+        tp = time.perf_counter()
+        rp = dm.reactor_run(cfg, prob, T0, P0, np.ones(n), Y0)
+        host_out = {k: v.cpu().numpy() for k, v in rp.items() if not k.startswith("_")}
+        torch.cuda.synchronize()
+        pcie_s = time.perf_counter() - tp
+        pcie = {"reactors_per_s": n / pcie_s, "seconds": pcie_s, "vs_value": (n / pcie_s) / (value / world),
+                "bytes_h2d": int(T0.nbytes + P0.nbytes + Y0.nbytes + prob.nbytes + 8 * n),
+                "bytes_d2h": int(sum(a.nbytes for a in host_out.values()))}
+        del rp, host_out
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         cpu = cpu_reactor_baseline(mech, T0, P0, Y0, prob, tau, args.cpu_seconds, args.cpu_sample)
     del sh, res
 
@@ -749,6 +790,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": tmax / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
