@@ -218,6 +218,9 @@ typedef struct {
  * inviscid momentum equation P + G u = P0 + G u0 any more (P0 + G u0)^2 < 4 G^2 R T / Wbar -- the
  * tube is choked (thermally, at the isothermal sound speed) and the run ends there */
 #define CKMI_RUN_CHOKED 5
+/* ckmi_psr_run: t_max was reached before the steady-state rule was met (the returned state is the
+ * transient's state at t_max, resid its scaled residual) */
+#define CKMI_RUN_NOT_STEADY 6
 
 /* Native Chemkin-II interpreter (host only, no GPU): the parse half of KINPreProcess
  * (chemkin_wrapper.py:303-316).  chem.inp text (+ optional therm.dat text; an inline THERMO block
@@ -304,6 +307,36 @@ int ckmi_reactor_run_ex(const ckmi_mech* mech, const ckmi_reactor_cfg* cfg, int3
                         const ckmi_reactor_ext* ext, double* tau, double* Tend, double* Pend, double* Vend,
                         double* Yend, int32_t* stats, int32_t nsave, const double* t_save, double* y_save,
                         void* stream);
+
+/* Batched perfectly stirred reactors (steady-state PSR, gas only, one effective inlet; the reference's
+ * stirreactors/PSR.py run one at a time).  Each reactor marches the open-reactor equations at constant
+ * pressure from its estimate until they are steady:
+ *   dY_k/dt  = (Y_k,in - Y_k) / tau + wdot_k W_k / rho
+ *   cp dT/dt = (H_in - sum_k Y_k,in h_k(T)) / tau - sum_k h_k wdot_k W_k / rho - Q / (rho V)    (energy = 1)
+ *   dT/dt    = 0, T = Tguess                                                                    (energy = 2)
+ * with rho = P Wbar / (R T), H_in = sum_k Y_k,in h_k(T_in) and Q = QLOS + HTC AREAQ (T - TAMB) from cfg
+ * (cal units as for the closed reactors).  mode 1: tau = tau_or_vol is given and V = tau mdot / rho;
+ * mode 2: V = tau_or_vol is given and tau = rho V / mdot follows the state.
+ * A state is steady when a fresh right-hand side f satisfies tau |f_k| <= ss_rtol |Y_k| + ss_atol for
+ * every species and tau |f_T| <= ss_rtol T.  The run ends at the first steady state (status CKMI_RUN_OK) or
+ * at t_max = cfg->t_end (0: 1000 tau) with CKMI_RUN_NOT_STEADY.  cfg->rtol / atol are the time integrator's
+ * tolerances; ignition detection, profiles and adaptive saving do not apply (CKMI_ERR_ARG).
+ * The result is the steady state the transient reaches FROM THE ESTIMATE: where a PSR has an ignited and an
+ * extinguished branch, a burnt estimate stays ignited and an unburnt one may blow out, whereas a damped
+ * Newton solver (Chemkin's TWOPNT) can land on either branch from the same estimate.
+ * KK + 1 <= 64 only (CKMI_ERR_UNSUPPORTED above).  All arrays are device pointers:
+ *   P, Tin, mdot, tau_or_vol, Tguess [n]; Yin, Yguess [n][KK]           inputs (dyn/cm2, K, g/s, s or cm3)
+ *   Tss [n], Yss [n][KK], rho [n] g/cm3, tau_res [n] s, vol [n] cm3     the returned state
+ *   resid [n]    the largest scaled residual of the rule at it (<= 1: steady)
+ *   stats [n][CKMI_NSTAT] */
+typedef struct {
+  int32_t mode; /* 1 residence time given, 2 volume given */
+  double ss_rtol, ss_atol;
+} ckmi_psr_cfg;
+int ckmi_psr_run(const ckmi_mech* mech, const ckmi_reactor_cfg* cfg, const ckmi_psr_cfg* psr, int32_t n,
+                 const double* P, const double* Tin, const double* Yin, const double* mdot,
+                 const double* tau_or_vol, const double* Tguess, const double* Yguess, double* Tss, double* Yss,
+                 double* rho, double* tau_res, double* vol, double* resid, int32_t* stats, void* stream);
 
 /* Heat rates of a single-zone engine run (problem 4) on its saved states, evaluated with the
  * integrator's own right-hand side: the output side of KINAll0D_GetEngineHeatRelease

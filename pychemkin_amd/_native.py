@@ -77,6 +77,12 @@ class ReactorExt(ct.Structure):
                 ("n_adap", _P), ("t_stop", _P)]
 
 
+class PsrCfg(ct.Structure):
+    _fields_ = [("mode", ct.c_int32), ("ss_rtol", ct.c_double), ("ss_atol", ct.c_double)]
+
+
+RUN_NOT_STEADY = 6  # CKMI_RUN_NOT_STEADY: a PSR reached t_max before the steady-state rule was met
+
 _lib: Optional[ct.CDLL] = None
 
 # every symbol include/ckmi.h declares, with its prototype
@@ -97,6 +103,7 @@ PROTOTYPES = {
                                         ct.POINTER(ReactorExt), _P, _P, _P, _P, _P, _P, ct.c_int32, _P, _P, _P]),
     "ckmi_engine_heat_rates": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.c_double, ct.c_double, _P, ct.c_int32, _P, _P,
                                           _P, _P, _P]),
+    "ckmi_psr_run": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.POINTER(PsrCfg), ct.c_int32] + [_P] * 15),
     "ckmi_set_reactor_path": (ct.c_int, [ct.c_int32]),
     "ckmi_big_max_image_bytes": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32]),
     "ckmi_set_rop_path": (ct.c_int, [ct.c_int32]),
@@ -495,6 +502,35 @@ class DeviceMechanism:
             res["t_save"] = ts
             res["y_save"] = ys
         return res
+
+    def psr_run(self, cfg: ReactorCfg, mode: int, P, Tin, Yin, mdot, tau_or_vol, Tguess, Yguess,
+                ss_rtol: float = 1e-8, ss_atol: float = 1e-14):
+        """n steady-state perfectly stirred reactors in one launch (ckmi_psr_run, include/ckmi.h).
+
+        mode 1: tau_or_vol is the residence time [s]; mode 2: the volume [cm3].  Yin / Yguess are [n][KK].
+        Each reactor returns the steady state its transient reaches from the estimate (Tguess, Yguess).
+        Returns a dict of device tensors: T, Y, rho, tau, vol, resid, stats."""
+        Tin = self._dev(Tin).reshape(-1)
+        n = Tin.numel()
+        vec = [self._dev(v).reshape(-1) for v in (P, mdot, tau_or_vol, Tguess)]
+        if any(v.numel() != n for v in vec):
+            raise ValueError("P, Tin, mdot, tau_or_vol and Tguess must all have n entries")
+        P, mdot, tv, Tg = vec
+        Yin = self._dev(Yin).reshape(n, self.KK)
+        Yg = self._dev(Yguess).reshape(n, self.KK)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        Tss, rho, tau, vol, resid = (torch.empty(n, **f64) for _ in range(5))
+        Yss = torch.empty((n, self.KK), **f64)
+        stats = torch.empty((n, NSTAT), dtype=torch.int32, device=self.device)
+        pc = PsrCfg(int(mode), float(ss_rtol), float(ss_atol))
+        with torch.cuda.device(self.device):
+            _check(lib().ckmi_psr_run(self._h, ct.byref(cfg), ct.byref(pc), n, _ptr(P), _ptr(Tin), _ptr(Yin),
+                                      _ptr(mdot), _ptr(tv), _ptr(Tg), _ptr(Yg), _ptr(Tss), _ptr(Yss), _ptr(rho),
+                                      _ptr(tau), _ptr(vol), _ptr(resid), _ptr(stats), _stream_ptr(self.device)),
+                   "ckmi_psr_run")
+        # the inputs stay referenced by the result (the launch is asynchronous on this stream)
+        return dict(T=Tss, Y=Yss, rho=rho, tau=tau, vol=vol, resid=resid, stats=stats,
+                    _inputs=[P, Tin, Yin, mdot, tv, Tg, Yg])
 
     def engine_heat_rates(self, cfg: ReactorCfg, T0: float, P0: float, Y0, t, y):
         """Apparent heat-release and wall heat-loss rates [erg/s] of an engine run (problem 4) on its

@@ -134,6 +134,147 @@ class BatchSweep:
         return self.run(T0, P0, Y0=Y0, V0=V0, problem=problem)
 
 
+@dataclass
+class PSRResult:
+    T: np.ndarray            # steady-state temperature [K]
+    Y: np.ndarray            # steady-state mass fractions [n, KK]
+    rho: np.ndarray          # density [g/cm3]
+    tau: np.ndarray          # residence time [s] (given, or rho V / mdot)
+    volume: np.ndarray       # reactor volume [cm3] (given, or tau mdot / rho)
+    resid: np.ndarray        # largest scaled residual of the steady-state rule (<= 1: steady)
+    mdot: np.ndarray         # exit mass flow rate [g/s] (= the inlet's: steady state)
+    P: np.ndarray            # pressure [dyn/cm2]
+    stats: np.ndarray        # [n, 8] int32 solver statistics (see _native.STAT_NAMES)
+    wt: np.ndarray
+
+    @property
+    def status(self) -> np.ndarray:
+        """0 steady; 6 (_native.RUN_NOT_STEADY) t_max reached first; 1-4 as for the closed reactors."""
+        return self.stats[:, 6]
+
+    @property
+    def X(self) -> np.ndarray:
+        x = self.Y / self.wt
+        return x / x.sum(axis=1, keepdims=True)
+
+
+class BatchPSR:
+    """Many independent steady-state perfectly stirred reactors in one launch per GPU.
+
+    Each reactor marches the open-reactor equations (include/ckmi.h ckmi_psr_run) from its estimate
+    until they are steady.  The result is therefore the steady state that the transient reaches FROM THE
+    ESTIMATE: on an S-curve a burnt estimate stays on the ignited branch, an unburnt one may blow out to
+    the inlet state, whereas Chemkin's damped Newton solver can land on either branch from the same
+    estimate.  ``estimate="burnt"`` is the estimate to use for the ignited branch.
+    """
+
+    def __init__(self, chem: Chemistry, mode: str = "residence_time", energy="ENERGY", ss_rtol: float = 1.0e-8,
+                 ss_atol: float = 1.0e-14, rtol: float = 1.0e-8, atol: float = 1.0e-14, t_max: float = 0.0,
+                 qloss: float = 0.0, htc: float = 0.0, areaq: float = 0.0, tamb: float = 300.0, gfac: float = 1.0,
+                 max_steps: int = 0, devices: Optional[Sequence[int]] = None):
+        """mode: "residence_time" (tau given) or "volume" (V given); energy: "ENERGY" or "TGIV" (the
+        temperature stays at the estimate's); ss_rtol / ss_atol: the steady-state rule; rtol / atol: the
+        time integrator; t_max: give up (status 6) after this time [s], 0 = 1000 residence times; qloss
+        [cal/s], htc [cal/(cm2 K s)], areaq [cm2], tamb [K]: Q = qloss + htc areaq (T - tamb)."""
+        if mode not in ("residence_time", "volume"):
+            raise ValueError('mode must be "residence_time" or "volume"')
+        self.chem = chem
+        self.mode = 1 if mode == "residence_time" else 2
+        self.ss_rtol, self.ss_atol = float(ss_rtol), float(ss_atol)
+        self.energy = ENERGIES[energy]
+        self.cfg = _native.make_cfg(energy=self.energy, t_end=t_max, atol=max(atol, 1e-20), rtol=max(rtol, 1e-12),
+                                    qloss=qloss, htc=htc, areaq=areaq, tamb=tamb, gfac=gfac, max_steps=max_steps)
+        self.devices = list(devices) if devices is not None else None
+
+    _devices = BatchSweep._devices
+
+    def _fractions(self, n, X, Y, what):
+        wt = self.chem.WT
+        if Y is None:
+            if X is None:
+                raise ValueError(f"{what}: X or Y is required")
+            Yv = np.broadcast_to(np.atleast_2d(np.asarray(X, dtype=np.float64)), (n, wt.size)) * wt
+            Y = Yv / Yv.sum(axis=1, keepdims=True)
+        return np.ascontiguousarray(np.broadcast_to(np.atleast_2d(np.asarray(Y, dtype=np.float64)), (n, wt.size)))
+
+    def burnt_estimate(self, P, Yin):
+        """End state (T, Y) of an adiabatic constant-pressure closed reactor started from the inlet
+        composition at 1600 K and run for 10 ms: one BatchSweep launch over the distinct (P, Yin) rows."""
+        key = np.concatenate([P[:, None], Yin], axis=1)
+        uniq, inv = np.unique(key, axis=0, return_inverse=True)
+        inv = np.asarray(inv).reshape(-1)
+        sweep = BatchSweep(self.chem, problem="CONP", energy="ENERGY", t_end=1.0e-2, atol=1e-12, rtol=1e-8,
+                           ignition=None, devices=self.devices)
+        r = sweep.run(np.full(uniq.shape[0], 1600.0), uniq[:, 0], Y0=uniq[:, 1:])
+        if np.any(r.status != 0):
+            raise _native.NativeError("the burnt estimate's closed reactors failed: status " + str(r.status.tolist()))
+        return r.T[inv], r.Y[inv]
+
+    def run(self, Tin, P, mdot, tau=None, volume=None, Xin=None, Yin=None, estimate="inlet",
+            T_estimate=None, X_estimate=None, Y_estimate=None) -> PSRResult:
+        """Solve reactors i = 0..n-1 (every input broadcasts over the reactors).
+
+        Tin [K], P [dyn/cm2], mdot [g/s], Xin or Yin: the one effective inlet of each reactor; tau [s] or
+        volume [cm3] by the mode.  estimate: "inlet" (the inlet state; T_estimate overrides its
+        temperature), "burnt" (burnt_estimate), or "given" with T_estimate and X_estimate / Y_estimate."""
+        import torch
+
+        tv = tau if self.mode == 1 else volume
+        if tv is None:
+            raise ValueError("tau is required" if self.mode == 1 else "volume is required")
+        arrs = np.broadcast_arrays(*[np.asarray(v, dtype=np.float64).reshape(-1) for v in (Tin, P, mdot, tv)])
+        n = arrs[0].size
+        if Xin is not None and np.ndim(Xin) == 2:
+            n = max(n, np.shape(Xin)[0])
+        if Yin is not None and np.ndim(Yin) == 2:
+            n = max(n, np.shape(Yin)[0])
+        if T_estimate is not None:
+            n = max(n, np.asarray(T_estimate).size)
+        Tin, P, mdot, tv = (np.broadcast_to(a, (n,)).copy() for a in arrs)
+        if np.any(Tin <= 0) or np.any(P <= 0) or np.any(mdot <= 0) or np.any(tv <= 0):
+            raise ValueError("Tin, P, mdot and tau / volume must be > 0")
+        Yin = self._fractions(n, Xin, Yin, "inlet")
+        if estimate == "burnt":
+            Tg, Yg = self.burnt_estimate(P, Yin)
+        elif estimate == "inlet":
+            Tg, Yg = Tin.copy(), Yin
+            if T_estimate is not None:
+                Tg = np.broadcast_to(np.asarray(T_estimate, dtype=np.float64).reshape(-1), (n,)).copy()
+        elif estimate == "given":
+            if T_estimate is None:
+                raise ValueError('estimate="given" needs T_estimate')
+            Tg = np.broadcast_to(np.asarray(T_estimate, dtype=np.float64).reshape(-1), (n,)).copy()
+            Yg = self._fractions(n, X_estimate, Y_estimate, "estimate")
+        else:
+            raise ValueError('estimate must be "inlet", "burnt" or "given"')
+        devs = self._devices()
+        if not devs:
+            raise _native.NativeError("no ROCm GPU visible: BatchPSR requires at least one MI355X")
+        shards = [np.arange(r, n, len(devs)) for r in range(len(devs))]
+        pending = []
+        for d, idx in zip(devs, shards):
+            if idx.size == 0:
+                continue
+            dm = self.chem.device_mechanism(d)
+            with torch.cuda.device(d):
+                res = dm.psr_run(self.cfg, self.mode, P[idx], Tin[idx], Yin[idx], mdot[idx], tv[idx], Tg[idx],
+                                 Yg[idx], ss_rtol=self.ss_rtol, ss_atol=self.ss_atol)
+            pending.append((idx, res))
+        wt = self.chem.WT
+        out = PSRResult(T=np.empty(n), Y=np.empty((n, wt.size)), rho=np.empty(n), tau=np.empty(n),
+                        volume=np.empty(n), resid=np.empty(n), mdot=mdot, P=P,
+                        stats=np.empty((n, _native.NSTAT), np.int32), wt=wt)
+        for idx, res in pending:
+            out.T[idx] = res["T"].cpu().numpy()
+            out.Y[idx] = res["Y"].cpu().numpy()
+            out.rho[idx] = res["rho"].cpu().numpy()
+            out.tau[idx] = res["tau"].cpu().numpy()
+            out.volume[idx] = res["vol"].cpu().numpy()
+            out.resid[idx] = res["resid"].cpu().numpy()
+            out.stats[idx] = res["stats"].cpu().numpy()
+        return out
+
+
 def afactor_sensitivity(chem: Chemistry, mixture: Mixture, factor: float = 1.001, reactions: Optional[Sequence[int]] = None,
                         volume: float = 1.0, **sweep_kw) -> Dict[str, np.ndarray]:
     """Brute-force A-factor sensitivity of the ignition delay (reference sensitivity.py:122-160).

@@ -51,9 +51,12 @@ constexpr int LDJ = WAVE + 1;  // leading dimension of the shared J scratch (odd
 struct RunCtx {
   int conp, energy;
   int pfr;                   // 1: problem 3, plug flow in x [cm] (conp = 1 as well); 2: problem 4,
-                             // single-zone IC engine (V(t) from cfg->eng; conp = 0)
+                             // single-zone IC engine (V(t) from cfg->eng; conp = 0); PSR instantiations
+                             // (problem 5, conp = 1): 3 residence time given, 4 volume given
   double G, Pm;              // plug flow: mass flux rho0 u0, momentum constant P0 + G u0;
-                             // engine: cp / cv (G) and temperature (Pm) of the initial charge (Woschni)
+                             // engine: cp / cv (G) and temperature (Pm) of the initial charge (Woschni);
+                             // PSR: 1 / tau (pfr 3) or mdot / V (pfr 4) in G, the inlet enthalpy H_in [erg/g] in
+                             // Pm; mass = tau mdot (pfr 3), V0 = the volume (pfr 4)
   int npv;     // VPRO / PPRO profile points (0 = constant V / P)
   int ntp;     // TPRO profile points (given-temperature runs, 0 = T from the state)
   int pslot;   // device slot of the reaction whose A is perturbed (-1 none), and ln(factor)
@@ -237,9 +240,16 @@ __device__ __noinline__ void gen_jac_terms(const MechView& V, const RunCtx& R, i
 // run-time (wave-uniform) flag and the Jacobian terms are a second pass over the reactions,
 // so the integrator has a single RHS call site and the register peak is that of one pass.
 // PF: plug flow compiled in (problem 3); without it R.pfr is never read and the branches vanish
-template <bool PL, bool PF>
+// PSR: the open well-stirred reactor (problem 5: R.pfr 3 / 4, conp = 1) replaces the closed CONP system:
+//   dY_k/dt = (Y_k,in - Y_k) / tau + wdot_k W_k / rho
+//   cp dT/dt = (H_in - sum_k Y_k,in h_k(T)) / tau - sum_k h_k wdot_k W_k / rho - Q / (rho V)
+// with 1 / tau = R.G (given) or R.G / rho (volume given), Yin the inlet mass fractions (wave's LDS slice).
+// The Jacobian gains the -1 / tau diagonal, the temperature row's inflow part and, with the volume given,
+// the derivatives of 1 / tau = mdot / (rho V): (1 / tau) / T by T and (1 / tau) Wbar / W_j by Y_j.
+template <bool PL, bool PF, bool PSR = false>
 __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R, double t, double yl,
-                                              const WaveLds& L, int oJ, int lane, int ncol, bool with_j
+                                              const WaveLds& L, int oJ, int lane, int ncol, bool with_j,
+                                              const double* Yin
 #ifdef CKMI_PHASE_TIMERS
                                               , unsigned long long (&sub)[9]
 #endif
@@ -434,6 +444,15 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
   const double rinv = 1.0 / rho;
   const double fY = isp ? L.wdot()[s] * Wk * rinv : 0.0;
   double fl = fY;
+  // open reactor: the inflow term of the species (fin) and the pieces of the temperature equation that
+  // depend on 1 / tau (fTin: inflow, fTq: heat loss per rho V), kept for the Jacobian
+  double rtau = 0.0, yin = 0.0, fin = 0.0, fTin = 0.0, fTq = 0.0;
+  if constexpr (PSR) {
+    rtau = R.pfr == 4 ? R.G * rinv : R.G;
+    yin = isp ? Yin[s] : 0.0;
+    fin = (yin - Yk) * rtau;
+    fl += fin;
+  }
   if (R.energy == 1) {
     const double cpk = th.cpR * RU * rw;
     const double hk = th.hRT * RU * T * rw;
@@ -449,7 +468,13 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
     double qloss = R.qloss, area = R.areaq, dummy;
     if (R.nq > 0) profile2_eval(R.cfg, R.nq, t, R.tsel, qloss, dummy);
     if (R.na > 0) pwl_eval(R.a_t, R.a_v, R.na, t, R.tsel, area, dummy);
-    const double mcp = R.mass * cpm;
+    double mass = R.mass;
+    if constexpr (PSR) {
+      if (R.pfr == 4) mass = rho * R.V0;
+      fTin = rtau * (R.Pm - wave_sum(yin * hk)) / cpm;
+      fT += fTin;
+    }
+    const double mcp = mass * cpm;
     double q1 = pfr ? 0.0 : R.htc * area * ERG_PER_CAL;  // plug flow: no wall heat loss on this path
     if (eng) {  // engine wall heat transfer replaces QLOS / HTC
       q1 = 0.0;
@@ -464,6 +489,7 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
       }
     } else if (!pfr) {
       fT -= (qloss * ERG_PER_CAL + q1 * (T - R.tamb)) / mcp;
+      if constexpr (PSR) fTq = -(qloss * ERG_PER_CAL + q1 * (T - R.tamb)) / mcp;
     }
     if (lane == 0) fl = fT;
     if (with_j) {
@@ -482,10 +508,34 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
       }
       const double s2 = wave_sum(ck * fY + ek * JkT);
       if (lane == 0) Jsh[0] = -s2 / cpm - q1 / mcp;
+      if constexpr (PSR) {  // the temperature row's inflow part (each lane touches only its own column)
+        const bool vgiven = R.pfr == 4;
+        const double cin = wave_sum(yin * cpk);
+        const double dr = vgiven ? fTin + fTq : 0.0;  // the terms proportional to 1 / rho
+        if (lane == 0) Jsh[0] += -rtau * cin / cpm + dr * invT;
+        if (isp) Jsh[(1 + s) * LDJ] += dr * Wbar * rw;
+      }
     }
   } else {
     if (lane == 0) fl = dTdt_given;  // 0 without TPRO
     if (with_j && isp) Jsh[1 + s] = L.dwdT()[s] * Wk * rinv + (conp ? fY * invT : 0.0);
+  }
+  if constexpr (PSR) {
+    if (with_j) {  // species rows: -1 / tau on the diagonal; volume given: d(1 / tau) / d(T, Y_j)
+      const bool vgiven = R.pfr == 4;
+      double* col = Jsh + (1 + s) * LDJ + 1;
+      if (isp) {
+        col[s] -= rtau;
+        if (vgiven) Jsh[1 + s] += fin * invT;
+      }
+      if (vgiven) {
+        const double wj = isp ? Wbar * rw : 0.0;
+        for (int k = 0; k < KK; ++k) {
+          const double fk = bcast(fin, 1 + k);
+          if (isp) col[k] += fk * wj;
+        }
+      }
+    }
   }
   wave_lds_sync();
   if (pfr) {  // d/dx = (rho / G) d/dt (a TPRO profile is already T(x)); the Jacobian alike

@@ -91,6 +91,16 @@ struct ReactorIO {
   double* t_stop;
 };
 
+// Open well-stirred reactor (problem 5, ckmi_psr_run): the closed-reactor fields carry the estimate
+// (T0, Y0), the pressure (P0), tau_or_vol (V0) and the steady state (T, Y); problem, tau, P and V are not
+// used (null).  These are the inlet and the PSR outputs.
+struct PsrIO : ReactorIO {
+  const double *Tin, *Yin, *mdot, *tau_or_vol;
+  double *rho, *tau_res, *vol, *resid;
+  int mode;  // 1 residence time given, 2 volume given
+  double ss_rtol, ss_atol;
+};
+
 // Integrator control state of one wave (wave-uniform scalars, kept in the wave's LDS slice).
 struct Ctl {
   int r, first, nflag, convfail, call_setup, failed, mm, ncf, nef, rc, isave, icrit, ncrit, status, nst, stopped;
@@ -129,7 +139,11 @@ enum {
   ST_STEP_COMPLETE,  // accept the step, choose the next h and q
   ST_STEP_END,       // outputs, ignition monitor, stops, critical-time restarts
   ST_FINISH,         // write the reactor's results
-  ST_EXIT
+  ST_EXIT,
+  // open well-stirred reactor (PSR instantiations only; handled ahead of the closed reactors' switch)
+  ST_PSR_SS_F,       // (f) fresh f at an accepted state: the steady-state rule
+  ST_PSR_POLISH_F,   // (f) f at a Newton iterate of f = 0
+  ST_PSR_END_F       // (f) f at the state a run without a steady state ends in (resid output)
 };
 
 }  // namespace ckmi

@@ -1,0 +1,277 @@
+"""Steady-state perfectly stirred reactors (drop-in for the reference's stirreactors/PSR.py) on the GPU.
+
+The four public models
+
+    PSR_SetResTime_EnergyConservation   PSR_SetVolume_EnergyConservation
+    PSR_SetResTime_FixedTemperature     PSR_SetVolume_FixedTemperature
+
+keep the reference's names and signatures; ``run()`` solves the reactor with one ckmi_psr_run launch
+(pychemkin_amd.batch.BatchPSR with n = 1; a sweep belongs in BatchPSR itself).
+
+Result semantic: the reactor's transient equations are marched from the ESTIMATE (the mixture the reactor
+was created with, see set_estimate_conditions) until they are steady, so the solution is the steady state
+that the transient reaches from that estimate.  Where a PSR has an ignited and an extinguished branch, a
+burnt estimate stays ignited and an unburnt one may blow out to the inlet state (CH4/air, 300 K inlet,
+tau = 1 ms from an unburnt 1700 K estimate does); the reference's TWOPNT Newton search can land on either
+branch from the same estimate.  set_estimate_conditions("HP") sets a burnt estimate.
+
+Reactor networks, clusters and surface chemistry are not covered.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple, Union
+
+import numpy as np
+
+from ..inlet import Stream
+from ..logger import logger
+from ..reactormodel import ReactorError
+from .openreactor import openreactor
+
+
+class perfectlystirredreactor(openreactor):
+    """Generic steady-state PSR (reference PSR.py:48-863)."""
+
+    def __init__(self, guessedmixture: Stream, label: Optional[str] = None):
+        super().__init__(guessedmixture, label if label is not None else "PSR")
+        self._problemtype = self.ProblemTypes["SETTAU"]
+        self._energytype = self.EnergyTypes["ENERGY"]
+        self._volume = 0.0
+        self._restime = 0.0
+        self._area = 0.0
+        self._heat_loss_rate = 0.0       # QLOS [cal/s]
+        self._heat_transfer_coeff = 0.0  # HTC [cal/(cm2 K s)]
+        self._ambient_temperature = 298.15
+        self._heat_transfer_area = 0.0   # AREAQ [cm2]
+        self._solution = None
+        # the burnt estimate's mass fractions as the GPU returned them (a Mixture renormalises what it is given)
+        self._estimate_Y = None
+
+    # ------------------------------------------------------------------ geometry
+    @property
+    def area(self) -> float:
+        """Reactive surface area [cm2] (kept for the interface; there is no surface chemistry here)."""
+        return self._area
+
+    @area.setter
+    def area(self, value: float = 0.0):
+        if value < 0.0:
+            raise ReactorError("reactor active surface area must be >= 0")
+        self._area = float(value)
+
+    @property
+    def volume(self) -> float:
+        """Reactor volume [cm3]."""
+        return self._volume
+
+    @volume.setter
+    def volume(self, value: float):
+        if value <= 0.0:
+            raise ReactorError("reactor volume must be > 0")
+        self._volume = float(value)
+        self.reactormixture.volume = float(value)
+        if "VOL" not in self._inputcheck:
+            self._inputcheck.append("VOL")
+
+    @property
+    def residence_time(self) -> float:
+        """Residence time [s]."""
+        return self._restime
+
+    @residence_time.setter
+    def residence_time(self, value: float):
+        if value <= 0.0:
+            raise ReactorError("reactor residence time must be > 0")
+        self._restime = float(value)
+        if "TAU" not in self._inputcheck:
+            self._inputcheck.append("TAU")
+
+    # ------------------------------------------------------------------ estimate
+    def set_estimate_conditions(self, option: str, guess_temp: Optional[float] = None):
+        """Transform the estimate (reference PSR.py:301-365).  "TT": the same composition at guess_temp.
+        "HP" / "TP": the reference takes an equilibrium state; here the burnt estimate of BatchPSR takes
+        its place (the end state of an adiabatic constant-pressure closed reactor started from the
+        estimate's composition at 1600 K for 10 ms; needs a GPU) -- "HP" with that state's temperature,
+        "TP" at guess_temp.  A burnt estimate keeps the reactor on its ignited branch."""
+        opt = option.upper()
+        if opt not in ("HP", "TP", "TT"):
+            raise ReactorError('estimate option must be "HP", "TP" or "TT"')
+        if opt != "HP":
+            if guess_temp is None:
+                logger.info("new gas temperature is not provided, the original temperature %s is applied",
+                            self.reactormixture.temperature)
+            elif guess_temp < 250.0:
+                logger.info("new gas temperature value is invalid, the original temperature %s is applied",
+                            self.reactormixture.temperature)
+            else:
+                self.reactormixture.temperature = float(guess_temp)
+        if opt in ("HP", "TP"):
+            from ..batch import BatchPSR
+
+            Tb, Yb = BatchPSR(self._chem).burnt_estimate(np.array([self.reactormixture.pressure]),
+                                                        np.array([self.reactormixture.Y]))
+            self.reactormixture.Y = Yb[0]
+            self._estimate_Y = Yb[0].copy()
+            if opt == "HP":
+                self.reactormixture.temperature = float(Tb[0])
+
+    def reset_estimate_temperature(self, temp: float):
+        if temp < 250.0:
+            raise ReactorError("the estimated gas temperature must be >= 250 K")
+        self.reactormixture.temperature = float(temp)
+
+    def reset_estimate_composition(self, fraction: Union[np.ndarray, List[Tuple[str, float]]], mode: str = "mole"):
+        m = mode.lower()
+        self._estimate_Y = None
+        if m == "mole":
+            self.reactormixture.X = fraction
+        elif m == "mass":
+            self.reactormixture.Y = fraction
+        else:
+            raise ReactorError('the mode of the new composition must be "mole" or "mass"')
+
+    # ------------------------------------------------------------------ run
+    def validate_inputs(self) -> int:
+        """Number of required inputs still missing, each logged: the residence time or the volume (by the
+        model) and at least one inlet."""
+        missing = super().validate_inputs()
+        if self.numbexternalinlets <= 0:
+            logger.error("missing required input: an external inlet (set_inlet)")
+            missing += 1
+        return missing
+
+    def _batch(self):
+        from ..batch import BatchPSR
+
+        ss_atol, ss_rtol = self.steady_state_tolerances
+        atol, rtol = self.time_stepping_tolerances
+        given_tau = self._problemtype == self.ProblemTypes["SETTAU"]
+        energy = self._energytype == self.EnergyTypes["ENERGY"]
+        return BatchPSR(self._chem, mode="residence_time" if given_tau else "volume",
+                        energy="ENERGY" if energy else "TGIV", ss_rtol=ss_rtol, ss_atol=ss_atol, rtol=rtol, atol=atol,
+                        qloss=self._heat_loss_rate if energy else 0.0,
+                        htc=self._heat_transfer_coeff if energy else 0.0,
+                        areaq=self._heat_transfer_area if energy else 0.0, tamb=self._ambient_temperature,
+                        gfac=self._gasratemultiplier)
+
+    def run(self) -> int:
+        """Solve the reactor on the GPU.  Returns 0 when a steady state was found, else the solver status
+        (_native.RUN_NOT_STEADY = 6: not steady within 1000 residence times)."""
+        if self.validate_inputs() != 0:
+            raise ReactorError(f"reactor {self.label}: required inputs are missing")
+        Tin, Yin, mdot = self.effective_inlet()
+        given_tau = self._problemtype == self.ProblemTypes["SETTAU"]
+        res = self._batch().run(Tin, self.reactormixture.pressure, mdot,
+                                tau=self._restime if given_tau else None, volume=None if given_tau else self._volume,
+                                Yin=Yin, estimate="given", T_estimate=self.reactormixture.temperature,
+                                Y_estimate=self.reactormixture.Y if self._estimate_Y is None else self._estimate_Y)
+        self._solution = res
+        self._numbsolutionpoints = 1
+        self._solution_rawarray = {"temperature": res.T.copy(), "pressure": res.P.copy(), "volume": res.volume.copy(),
+                                   "flowrate": res.mdot.copy()}
+        self.setrunstatus(int(res.status[0]))
+        if self.runstatus != 0:
+            logger.error("reactor %s: no steady state (status %d, scaled residual %.3e)", self.label, self.runstatus,
+                         float(res.resid[0]))
+        return self.runstatus
+
+    def process_solution(self) -> Stream:
+        """The steady-state solution as a Stream that carries the exit mass flow rate."""
+        if self._solution is None:
+            raise ReactorError(f"reactor {self.label} has no solution: call run() first")
+        r = self._solution
+        out = Stream(self._chem, label=self.label + "_exit")
+        out.pressure = float(r.P[0])
+        out.temperature = float(r.T[0])
+        out.Y = np.maximum(r.Y[0], 0.0)
+        out.volume = float(r.volume[0])
+        out.mass_flowrate = float(r.mdot[0])
+        self._solution_mixturearray = [out]
+        return out
+
+
+class _HeatTransfer:
+    """The four heat-transfer properties of the energy-conservation models:
+    Q = heat_loss_rate + heat_transfer_coefficient heat_transfer_area (T - ambient_temperature)."""
+
+    @property
+    def heat_loss_rate(self) -> float:
+        """QLOS [cal/s]."""
+        return self._heat_loss_rate
+
+    @heat_loss_rate.setter
+    def heat_loss_rate(self, value: float):
+        self._heat_loss_rate = float(value)
+
+    @property
+    def heat_transfer_coefficient(self) -> float:
+        """HTC [cal/(cm2 K s)]."""
+        return self._heat_transfer_coeff
+
+    @heat_transfer_coefficient.setter
+    def heat_transfer_coefficient(self, value: float = 0.0):
+        if value < 0.0:
+            raise ReactorError("heat transfer coefficient must be >= 0")
+        self._heat_transfer_coeff = float(value)
+
+    @property
+    def ambient_temperature(self) -> float:
+        """TAMB [K]."""
+        return self._ambient_temperature
+
+    @ambient_temperature.setter
+    def ambient_temperature(self, value: float = 0.0):
+        if value <= 0.0:
+            raise ReactorError("ambient temperature must be > 0")
+        self._ambient_temperature = float(value)
+
+    @property
+    def heat_transfer_area(self) -> float:
+        """AREAQ [cm2]."""
+        return self._heat_transfer_area
+
+    @heat_transfer_area.setter
+    def heat_transfer_area(self, value: float = 0.0):
+        if value < 0.0:
+            raise ReactorError("heat transfer area must be >= 0")
+        self._heat_transfer_area = float(value)
+
+
+class PSR_SetResTime_EnergyConservation(_HeatTransfer, perfectlystirredreactor):
+    """PSR with a given residence time, solving the energy equation."""
+
+    def __init__(self, guessedmixture: Stream, label: Optional[str] = None):
+        super().__init__(guessedmixture, label if label is not None else "PSR")
+        self._problemtype = self.ProblemTypes["SETTAU"]
+        self._energytype = self.EnergyTypes["ENERGY"]
+        self._requiredlist = ["TAU"]
+
+
+class PSR_SetVolume_EnergyConservation(_HeatTransfer, perfectlystirredreactor):
+    """PSR with a given volume, solving the energy equation."""
+
+    def __init__(self, guessedmixture: Stream, label: Optional[str] = None):
+        super().__init__(guessedmixture, label if label is not None else "PSR")
+        self._problemtype = self.ProblemTypes["SETVOL"]
+        self._energytype = self.EnergyTypes["ENERGY"]
+        self._requiredlist = ["VOL"]
+
+
+class PSR_SetResTime_FixedTemperature(perfectlystirredreactor):
+    """PSR with a given residence time at the estimate's temperature."""
+
+    def __init__(self, guessedmixture: Stream, label: Optional[str] = None):
+        super().__init__(guessedmixture, label if label is not None else "PSR")
+        self._problemtype = self.ProblemTypes["SETTAU"]
+        self._energytype = self.EnergyTypes["GivenT"]
+        self._requiredlist = ["TAU"]
+
+
+class PSR_SetVolume_FixedTemperature(perfectlystirredreactor):
+    """PSR with a given volume at the estimate's temperature."""
+
+    def __init__(self, guessedmixture: Stream, label: Optional[str] = None):
+        super().__init__(guessedmixture, label if label is not None else "PSR")
+        self._problemtype = self.ProblemTypes["SETVOL"]
+        self._energytype = self.EnergyTypes["GivenT"]
+        self._requiredlist = ["VOL"]
