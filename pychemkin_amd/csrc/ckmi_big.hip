@@ -872,6 +872,18 @@ __global__ __launch_bounds__(NT, 1) void big_reactor_kernel(MechImage img, BigLd
         }
         case ST_NLS_ATTEMPT: {
           b.y = b.zn[0];
+          // a stale Jacobian (oracle nls_setup's jbad: none of its inputs depends on f) is decided here, so
+          // that f and J of the point come from one evaluation (rhs_big returns f with the Jacobian)
+          if (c.call_setup) {
+            const double dgamma = fabs(S.gamma / S.gammap - 1.0);
+            const int jbad = S.nst == 0 || S.nst >= S.nstlj + MSBJ || (c.convfail == CF_BAD_J && dgamma < DGMAX) ||
+                             c.convfail == CF_OTHER;
+            if (jbad) {
+              REQUEST_F(S.tn, b.y, ST_NLS_J);
+              with_j = true;
+              break;
+            }
+          }
           REQUEST_F(S.tn, b.y, ST_NLS_F);
           break;
         }
@@ -885,20 +897,13 @@ __global__ __launch_bounds__(NT, 1) void big_reactor_kernel(MechImage img, BigLd
             st = ST_NEWTON_ITER;
             break;
           }
-          const double dgamma = fabs(S.gamma / S.gammap - 1.0);
-          const int jbad = S.nst == 0 || S.nst >= S.nstlj + MSBJ || (c.convfail == CF_BAD_J && dgamma < DGMAX) ||
-                           c.convfail == CF_OTHER;
-          if (jbad) {
-            REQUEST_F(S.tn, b.y, ST_NLS_J);
-            with_j = true;
-          } else {
-            S.jcur = 0;
-            st = ST_SETUP;
-          }
+          S.jcur = 0;  // a set-up with the parked Jacobian (ST_NLS_ATTEMPT found it still good)
+          st = ST_SETUP;
           break;
         }
         case ST_NLS_J: {
-          S.nfe++;
+          b.ftemp = fe;  // f of the same evaluation
+          S.nfe += 2;    // as the oracle counts a Jacobian event: the step's f and the Jacobian's own evaluation
           S.nje++;
           S.nstlj = S.nst;
           S.jcur = 1;

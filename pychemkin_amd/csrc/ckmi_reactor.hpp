@@ -195,8 +195,8 @@ __device__ __forceinline__ void jac_scatter(const MechView& V, int oJ, int nr, i
   }
 }
 
-// Jacobian terms of a general reaction (FORD / RORD / non-integral coefficients): dwdot/dT and
-// dq/dC_j through the orders, scattered with the real coefficients (oracle reactor_rhs).
+// Jacobian-pass terms of a general reaction (FORD / RORD / non-integral coefficients): wdot, dwdot/dT
+// and dq/dC_j through the orders, scattered with the real coefficients (oracle reactor_rhs).
 __device__ __noinline__ void gen_jac_terms(const MechView& V, const RunCtx& R, int i, uint32_t inf, double T,
                                            double lnT, double invT, double lnPRT, double P, const double* C,
                                            const WaveLds& L, int oJ, int conp) {
@@ -206,6 +206,9 @@ __device__ __noinline__ void gen_jac_terms(const MechView& V, const RunCtx& R, i
   const double* e2t = V.e2t();
   const int nr = (int)g[0], np = (int)g[1];
   const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
+  // the Jacobian pass is the call's only pass over the reactions: wdot rides on it
+  for (int u = 0; u < nr; ++u) atomicAdd(&L.wdot()[(int)g[2 + 3 * u]], -g[3 + 3 * u] * q);
+  for (int u = 0; u < np; ++u) atomicAdd(&L.wdot()[(int)g[GEN_P + 3 * u]], g[GEN_P + 1 + 3 * u] * q);
   double dqdT = e.mfac * (e.kf * e.dlkf * e.pf - e.kr * e.dlkr * e.pr);
   if (conp) {
     double of = 0.0, orr = 0.0;
@@ -237,8 +240,10 @@ __device__ __noinline__ void gen_jac_terms(const MechView& V, const RunCtx& R, i
 // Right-hand side f(t, y) (one component per lane, lane 0 = T) and, if with_j, the
 // approximate analytic Jacobian into the workgroup's shared J scratch (column-major, the
 // caller holds its lock).  Same formulation as oracle/ckoracle.c reactor_rhs().  with_j is a
-// run-time (wave-uniform) flag and the Jacobian terms are a second pass over the reactions,
-// so the integrator has a single RHS call site and the register peak is that of one pass.
+// run-time (wave-uniform) flag that selects one of two passes over the reactions -- the plain one
+// (wdot only) or the Jacobian one, which scatters wdot next to dwdot/dT and dq/dC from the same q --
+// so the integrator has a single RHS call site, the register peak is that of one pass, and the f a
+// with_j call returns is complete (the integrator takes f and J of a stale-Jacobian point from one call).
 // PF: plug flow compiled in (problem 3); without it R.pfr is never read and the branches vanish
 // PSR: the open well-stirred reactor (problem 5: R.pfr 3 / 4, conp = 1) replaces the closed CONP system:
 //   dY_k/dt = (Y_k,in - Y_k) / tau + wdot_k W_k / rho
@@ -353,45 +358,46 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
   wave_lds_sync();
   SUB_PHASE(0);
   const int IIp = V.IIp;
-  for (int base = 0; base < IIp; base += WAVE) {
-    const int i = base + lane;
-    const uint32_t inf = V.info()[i];
-    const int nr = rx_nr(inf), np = rx_np(inf);
-    if constexpr (PL) {
-      if (inf & RX_GEN) {  // FORD / RORD / non-integral coefficients: real nu and orders
-        const double* g;
-        const Rxn e = eval_gen_img(V, i, inf, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), false, R.pslot,
-                                   R.plnf, R.gfac, g);
-        const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
+  if (!with_j) {
+    for (int base = 0; base < IIp; base += WAVE) {
+      const int i = base + lane;
+      const uint32_t inf = V.info()[i];
+      const int nr = rx_nr(inf), np = rx_np(inf);
+      if constexpr (PL) {
+        if (inf & RX_GEN) {  // FORD / RORD / non-integral coefficients: real nu and orders
+          const double* g;
+          const Rxn e = eval_gen_img(V, i, inf, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), false, R.pslot,
+                                     R.plnf, R.gfac, g);
+          const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
 #pragma unroll
-        for (int u = 0; u < GEN_SLOTS; ++u) {
-          if (u < (int)g[0]) atomicAdd(&L.wdot()[(int)g[2 + 3 * u]], -g[3 + 3 * u] * q);
-          if (u < (int)g[1]) atomicAdd(&L.wdot()[(int)g[GEN_P + 3 * u]], g[GEN_P + 1 + 3 * u] * q);
+          for (int u = 0; u < GEN_SLOTS; ++u) {
+            if (u < (int)g[0]) atomicAdd(&L.wdot()[(int)g[2 + 3 * u]], -g[3 + 3 * u] * q);
+            if (u < (int)g[1]) atomicAdd(&L.wdot()[(int)g[GEN_P + 3 * u]], g[GEN_P + 1 + 3 * u] * q);
+          }
         }
       }
-    }
-    if (nr + np != 0) {
-      const uint32_t rs = V.rsp()[i], ps = V.psp()[i], nuw = V.nu()[i];
-      const Rxn e = eval_rxn_img<PL>(V, i, inf, rs, ps, nuw, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), false,
-                                 R.pslot, R.plnf, R.gfac);
-      const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
-      const bool s23 = __ballot(nr > 2 || np > 2) != 0;  // wave-uniform: slots 2, 3 in use anywhere
+      if (nr + np != 0) {
+        const uint32_t rs = V.rsp()[i], ps = V.psp()[i], nuw = V.nu()[i];
+        const Rxn e = eval_rxn_img<PL>(V, i, inf, rs, ps, nuw, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), false,
+                                   R.pslot, R.plnf, R.gfac);
+        const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
+        const bool s23 = __ballot(nr > 2 || np > 2) != 0;  // wave-uniform: slots 2, 3 in use anywhere
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (u >= 2 && !s23) break;
-        if (u < nr) atomicAdd(&L.wdot()[sp_of(rs, u)], -q);
-        if (u < np) atomicAdd(&L.wdot()[sp_of(ps, u)], q);
+        for (int u = 0; u < 4; ++u) {
+          if (u >= 2 && !s23) break;
+          if (u < nr) atomicAdd(&L.wdot()[sp_of(rs, u)], -q);
+          if (u < np) atomicAdd(&L.wdot()[sp_of(ps, u)], q);
+        }
       }
-    }
 #ifdef CKMI_PHASE_TIMERS
-    if (base / WAVE < 6) {
-      const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-      sub[3 + base / WAVE] += t2 - tsub;
-      tsub = t2;
-    }
+      if (base / WAVE < 6) {
+        const unsigned long long t2 = __builtin_amdgcn_s_memtime();
+        sub[3 + base / WAVE] += t2 - tsub;
+        tsub = t2;
+      }
 #endif
-  }
-  if (with_j) {
+    }
+  } else {
     for (int base = 0; base < IIp; base += WAVE) {
       const int i = base + lane;
       const uint32_t inf = V.info()[i];
@@ -413,10 +419,18 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
         dqdT -= e.mfac * (ordf * e.kf * e.pf - ordr * e.kr * e.pr) * invT;
         if (rx_type(inf) == 1) dqdT -= q * invT;
       }
+      const bool s23 = __ballot(nr > 2 || np > 2) != 0;  // wave-uniform, as in the plain pass
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        if (u < nr) atomicAdd(&L.dwdT()[sp_of(rs, u)], -dqdT);
-        if (u < np) atomicAdd(&L.dwdT()[sp_of(ps, u)], dqdT);
+        if (u >= 2 && !s23) break;
+        if (u < nr) {
+          atomicAdd(&L.wdot()[sp_of(rs, u)], -q);
+          atomicAdd(&L.dwdT()[sp_of(rs, u)], -dqdT);
+        }
+        if (u < np) {
+          atomicAdd(&L.wdot()[sp_of(ps, u)], q);
+          atomicAdd(&L.dwdT()[sp_of(ps, u)], dqdT);
+        }
       }
       // dq/dC_j for every reactant slot (forward) and product slot (reverse): the product of
       // the other three slots' concentrations (a species in two slots contributes twice)
@@ -728,7 +742,9 @@ struct NewtonMatrixGJ64 {
   // orow: LDS byte offset of an N-double scratch row of the calling wave (16-byte aligned).
   // The pivot row is broadcast through it: the pivot lane writes its row with ds_write_b128,
   // every lane reads it back with broadcast ds_read_b128 -- 1 LDS instruction per element
-  // instead of 2 v_readlane + the SGPR-forwarding wait of a register broadcast.
+  // instead of 2 v_readlane + the SGPR-forwarding wait of a register broadcast (the readlane form,
+  // pair by pair inside the elimination loop, measured 1.0 % slower on configs[2]:
+  // profiles/r07b_ab_gj_readlane_pivot_row.log).
   __device__ __forceinline__ bool factor(int lane_in, int n, int orow) {
     const int lane = opaque_lane(lane_in);
     bool pivoted = lane >= N;

@@ -519,6 +519,26 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
         }
         case ST_NLS_ATTEMPT: {
           b.y = b.zn[0];
+          // a stale Jacobian (oracle nls_setup's jbad: none of its inputs depends on f) is decided here, so
+          // that f and J of the point come from ONE evaluation, its reactions visited once
+          if (c.call_setup) {
+            const double dgamma = fabs(S.gamma / S.gammap - 1.0);
+            const int jbad = S.nst == 0 || S.nst >= S.nstlj + MSBJ || (c.convfail == CF_BAD_J && dgamma < DGMAX) ||
+                             c.convfail == CF_OTHER;
+            if (jbad) {
+              // exclusive use of the workgroup's J scratch until it is copied out
+              for (;;) {
+                int got = 0;
+                if (lane == 0) got = atomicCAS(lds_at<int>(olock), 0, 1) == 0;
+                if (uni(bcast(got, 0))) break;
+                __builtin_amdgcn_s_sleep(4);
+              }
+              wave_lds_sync();
+              REQUEST_F(S.tn, b.y, ST_NLS_J);
+              with_j = true;
+              break;
+            }
+          }
           REQUEST_F(S.tn, b.y, ST_NLS_F);
           break;
         }
@@ -532,27 +552,12 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
             st = ST_NEWTON_ITER;
             break;
           }
-          const double dgamma = fabs(S.gamma / S.gammap - 1.0);
-          const int jbad = S.nst == 0 || S.nst >= S.nstlj + MSBJ || (c.convfail == CF_BAD_J && dgamma < DGMAX) ||
-                           c.convfail == CF_OTHER;
-          if (jbad) {
-            // exclusive use of the workgroup's J scratch until it is copied out
-            for (;;) {
-              int got = 0;
-              if (lane == 0) got = atomicCAS(lds_at<int>(olock), 0, 1) == 0;
-              if (uni(bcast(got, 0))) break;
-              __builtin_amdgcn_s_sleep(4);
-            }
-            wave_lds_sync();
-            REQUEST_F(S.tn, b.y, ST_NLS_J);
-            with_j = true;
-          } else {
-            S.jcur = 0;
-            st = ST_SETUP;
-          }
+          S.jcur = 0;  // a set-up with the parked Jacobian (ST_NLS_ATTEMPT found it still good)
+          st = ST_SETUP;
           break;
         }
         case ST_NLS_J: {
+          b.ftemp = fe;  // f of the same evaluation
           {
             const double* Jsh = lds_at<const double>(oJ);
 #pragma unroll 2
@@ -560,7 +565,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           }
           wave_lds_sync();
           if (lane == 0) atomicExch(lds_at<int>(olock), 0);
-          S.nfe++;
+          S.nfe += 2;  // as the oracle counts a Jacobian event: the step's f and the Jacobian's own evaluation
           S.nje++;
           S.nstlj = S.nst;
           S.jcur = 1;
