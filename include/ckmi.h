@@ -250,6 +250,9 @@ int ckmi_mech_sizes(const ckmi_mech* mech, int32_t* KK, int32_t* II);
 /* A-factor get/set (original reaction order, 0-based); set takes effect for later calls. */
 int ckmi_get_arrhenius(const ckmi_mech* mech, double* A, double* b, double* E_R);
 int ckmi_set_afactor(ckmi_mech* mech, int32_t irxn, double A);
+/* Device slot of every reaction (slot[II], original order): the rate kernels visit slots in strips of 64,
+ * elementary reactions first, then third-body, then falloff.  A diagnostic for tests and profiling. */
+int ckmi_reaction_slots(const ckmi_mech* mech, int32_t* slot);
 
 /* Species thermo per state: cp/R, h/RT, s/R  (device, [KK][n] each; any may be NULL). */
 int ckmi_species_thermo(const ckmi_mech* mech, int32_t n, const double* T, double* cp_R, double* h_RT,

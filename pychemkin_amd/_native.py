@@ -94,6 +94,7 @@ PROTOTYPES = {
     "ckmi_mech_sizes": (ct.c_int, [_P, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32)]),
     "ckmi_get_arrhenius": (ct.c_int, [_P, _P, _P, _P]),
     "ckmi_set_afactor": (ct.c_int, [_P, ct.c_int32, ct.c_double]),
+    "ckmi_reaction_slots": (ct.c_int, [_P, _P]),
     "ckmi_species_thermo": (ct.c_int, [_P, ct.c_int32, _P, _P, _P, _P, _P]),
     "ckmi_rop_thermo": (ct.c_int, [_P, ct.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "ckmi_reaction_rates": (ct.c_int, [_P, ct.c_int32, _P, _P, _P, _P, _P, _P]),
@@ -381,6 +382,12 @@ class DeviceMechanism:
         A, b, E = (np.zeros(self.II) for _ in range(3))
         _check(lib().ckmi_get_arrhenius(self._h, A.ctypes.data, b.ctypes.data, E.ctypes.data), "ckmi_get_arrhenius")
         return A, b, E
+
+    def slot_of(self) -> np.ndarray:
+        """Device slot of every reaction (original order); slot // 64 is the strip that evaluates it."""
+        s = np.zeros(self.II, np.int32)
+        _check(lib().ckmi_reaction_slots(self._h, s.ctypes.data), "ckmi_reaction_slots")
+        return s
 
     def set_afactor(self, irxn: int, A: float) -> None:
         with torch.cuda.device(self.device):

@@ -108,9 +108,9 @@ __global__ __launch_bounds__(WAVE) void engine_heat_kernel(MechImage img, const 
     wave_lds_sync();
 #ifdef CKMI_PHASE_TIMERS
     unsigned long long sub[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const double fl = reactor_rhs<PL, true>(V, R, t, yl, L, 0, lane, WAVE, false, nullptr, sub);
+    const double fl = reactor_rhs<PL, true>(V, R, t, yl, L, 0, WAVE, false, nullptr, sub);
 #else
-    const double fl = reactor_rhs<PL, true>(V, R, t, yl, L, 0, lane, WAVE, false, nullptr);
+    const double fl = reactor_rhs<PL, true>(V, R, t, yl, L, 0, WAVE, false, nullptr);
 #endif
     const double T = bcast(yl, 0), dTdt = bcast(fl, 0);
     const double Yk = isp ? yl : 0.0;
@@ -1126,6 +1126,12 @@ int ckmi_get_arrhenius(const ckmi_mech* m, double* A, double* b, double* E) {
     if (b) b[i] = m->b_orig[i];
     if (E) E[i] = m->E_orig[i];
   }
+  return CKMI_OK;
+}
+
+int ckmi_reaction_slots(const ckmi_mech* m, int32_t* slot) {
+  if (!m || !slot) return fail(CKMI_ERR_ARG, "null mech or slot array");
+  for (int i = 0; i < m->II; ++i) slot[i] = m->slot_of[i];
   return CKMI_OK;
 }
 

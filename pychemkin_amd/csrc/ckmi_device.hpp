@@ -68,6 +68,17 @@ __device__ __forceinline__ double bcast(double v, int lane) {
 }
 __device__ __forceinline__ int bcast(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 
+// The lane index, recomputed where it is used: two v_mbcnt instead of a value that lives across the
+// persistent reactor loop.  There the register allocator parks a long-lived lane index in scratch and
+// reloads it (scratch_load + s_waitcnt vmcnt(0)) in front of every strip of the RHS, every solve and every
+// set-up.  Volatile asm (the form of __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))):
+// the builtins are pure, so the optimiser would merge all their uses back into one value and park that.
+__device__ __forceinline__ int wave_lane() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
 // Cross-lane reductions on the DPP path (quad_perm / row_half_mirror / row_mirror inside each
 // 16-lane row, then four readlanes across rows): no LDS round trips, unlike ds_bpermute-based
 // __shfl_xor.  Every lane of a row computes the same commutative pairings, so the result is

@@ -159,7 +159,14 @@ constexpr double E2T_L_HI = 0x1.62e42fefa39efp-6;         // (ln 2)_hi / 32
 constexpr double E2T_L_LO = 0x1.abc9e3b39803fp-61;        // (ln 2)_lo / 32
 __device__ __forceinline__ double fexp(double x, const double* e2t) {
   constexpr double INV_L = E2T_INV_L, L_HI = E2T_L_HI, L_LO = E2T_L_LO;
-  x = x < -1000.0 ? -1000.0 : (x > 1000.0 ? 1000.0 : x);
+  // saturation: beyond +/-1000 only the high word is replaced, by that of +/-1000 (the low word stays, so the
+  // clamped value lies in [1000, 1000.0002): e^x over- or underflows there all the same).  One compare of |x|
+  // (false for a NaN, which passes through), one bit-field insert, one select; inside +/-1000 x is untouched.
+  {
+    const int hi = __double2hiint(x);
+    const int sat = (hi & (int)0x80000000) | 0x408F4000;  // high word of copysign(1000.0, x)
+    x = __hiloint2double(fabs(x) > 1000.0 ? sat : hi, __double2loint(x));
+  }
   const double kd = __builtin_rint(x * INV_L);
   const double r = fma(kd, -L_LO, fma(kd, -L_HI, x));
   const int k = (int)kd;
@@ -211,8 +218,11 @@ __device__ __forceinline__ Rxn eval_rxn_img(const MechView& V, int i, uint32_t i
                                             const double* pA = nullptr) {
   constexpr double INV_LN10 = 0.43429448190325176;
   const int type = rx_type(inf);
-  // pslot / plnf: per-reactor A-factor perturbation (brute-force sensitivity)
-  const double lnA = (PRE ? pA[0] : V.lnA()[i]) + (i == pslot ? plnf : 0.0);
+  // pslot / plnf: per-reactor A-factor perturbation (brute-force sensitivity).  Behind a test of pslot
+  // alone: the wave kernel passes a wave-uniform pslot that is -1 in every strip but the slot's own, and
+  // those strips skip the compare, the select and the read of plnf as a scalar branch
+  double lnA = PRE ? pA[0] : V.lnA()[i];
+  if (pslot >= 0) lnA += (i == pslot ? plnf : 0.0);
   const double b = PRE ? pA[1] : V.beta()[i], Ea = PRE ? pA[2] : V.Ea()[i];
   double lnkinf = lnA + b * lnT - Ea * invT;
   double dlkf = (b + Ea * invT) * invT;

@@ -253,7 +253,7 @@ __device__ __noinline__ void gen_jac_terms(const MechView& V, const RunCtx& R, i
 // the derivatives of 1 / tau = mdot / (rho V): (1 / tau) / T by T and (1 / tau) Wbar / W_j by Y_j.
 template <bool PL, bool PF, bool PSR = false>
 __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R, double t, double yl,
-                                              const WaveLds& L, int oJ, int lane, int ncol, bool with_j,
+                                              const WaveLds& L, int oJ, int ncol, bool with_j,
                                               const double* Yin
 #ifdef CKMI_PHASE_TIMERS
                                               , unsigned long long (&sub)[9]
@@ -271,8 +271,11 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
 #define SUB_PHASE(k) (void)0
 #endif
   const int KK = V.KK;
-  const bool isp = lane >= 1 && lane <= KK;
-  const int s = isp ? lane - 1 : 0;
+  // the lane index is recomputed here, in every strip and after the strips (wave_lane): a value carried
+  // from the kernel's prologue is reloaded from scratch at each of these places
+  int lane = wave_lane();
+  bool isp = lane >= 1 && lane <= KK;
+  int s = isp ? lane - 1 : 0;
   double T = bcast(yl, 0), dTdt_given = 0.0;
   if (R.ntp > 0) profile_eval(R.cfg, R.ntp, t, R.tsel, T, T, dTdt_given);  // TPRO: T(t) is given
   const double Yk = isp ? yl : 0.0;
@@ -358,15 +361,19 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
   wave_lds_sync();
   SUB_PHASE(0);
   const int IIp = V.IIp;
+  // A-factor perturbation: the slot is read once per call, and only the strip that holds it (a wave-uniform
+  // test) passes it on; the others carry no compare, select or LDS read for it (eval_rxn_img)
+  const int pslot = uni(R.pslot);
   if (!with_j) {
     for (int base = 0; base < IIp; base += WAVE) {
-      const int i = base + lane;
+      const int i = base + wave_lane();
+      const int psl = (unsigned)(pslot - base) < (unsigned)WAVE ? pslot : -1;
       const uint32_t inf = V.info()[i];
       const int nr = rx_nr(inf), np = rx_np(inf);
       if constexpr (PL) {
         if (inf & RX_GEN) {  // FORD / RORD / non-integral coefficients: real nu and orders
           const double* g;
-          const Rxn e = eval_gen_img(V, i, inf, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), false, R.pslot,
+          const Rxn e = eval_gen_img(V, i, inf, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), false, psl,
                                      R.plnf, R.gfac, g);
           const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
 #pragma unroll
@@ -379,12 +386,15 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
       if (nr + np != 0) {
         const uint32_t rs = V.rsp()[i], ps = V.psp()[i], nuw = V.nu()[i];
         const Rxn e = eval_rxn_img<PL>(V, i, inf, rs, ps, nuw, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), false,
-                                   R.pslot, R.plnf, R.gfac);
+                                   psl, R.plnf, R.gfac);
         const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
         const bool s23 = __ballot(nr > 2 || np > 2) != 0;  // wave-uniform: slots 2, 3 in use anywhere
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           if (u >= 2 && !s23) break;
+          // (one predicate per atomic: unpredicated atomics, with unused slots adding into the dummy
+          // species' row, measured 11 % slower on configs[2] -- the dummy address serialises;
+          // profiles/r08_ab_steps.log)
           if (u < nr) atomicAdd(&L.wdot()[sp_of(rs, u)], -q);
           if (u < np) atomicAdd(&L.wdot()[sp_of(ps, u)], q);
         }
@@ -399,7 +409,8 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
     }
   } else {
     for (int base = 0; base < IIp; base += WAVE) {
-      const int i = base + lane;
+      const int i = base + wave_lane();
+      const int psl = (unsigned)(pslot - base) < (unsigned)WAVE ? pslot : -1;
       const uint32_t inf = V.info()[i];
       const int nr = rx_nr(inf), np = rx_np(inf);
       if constexpr (PL) {
@@ -411,7 +422,7 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
       if (nr + np == 0) continue;
       const uint32_t rs = V.rsp()[i], ps = V.psp()[i], nuw = V.nu()[i];
       const Rxn e = eval_rxn_img<PL>(V, i, inf, rs, ps, nuw, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), true,
-                                 R.pslot, R.plnf, R.gfac);
+                                 psl, R.plnf, R.gfac);
       const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
       double dqdT = e.mfac * (e.kf * e.dlkf * e.pf - e.kr * e.dlkr * e.pr);
       if (conp) {
@@ -455,6 +466,9 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
   }
   wave_lds_sync();
   SUB_PHASE(1);
+  lane = wave_lane();
+  isp = lane >= 1 && lane <= KK;
+  s = isp ? lane - 1 : 0;
   const double rinv = 1.0 / rho;
   const double fY = isp ? L.wdot()[s] * Wk * rinv : 0.0;
   double fl = fY;
@@ -695,10 +709,12 @@ __device__ __forceinline__ void elem_project_wave(const MechView& V, int npe, co
 // U / u_kk right of it, 1 / u_kk in rdiag): both triangular sweeps then broadcast from a
 // compile-time lane and never touch LDS memory.
 
-// The lane index laundered through an empty volatile asm: comparisons of it with the
+// A value laundered through an empty volatile asm: comparisons of the lane index with the
 // unrolled loop constants below must be computed where they are used.  Left visible, LICM
 // hoists all N (lane == j) masks / identity entries out of the persistent reactor loop and
-// keeps them live (spilled) across the whole integrator.
+// keeps them live (spilled) across the whole integrator.  The Newton matrix forms below take the
+// lane itself from wave_lane() (opaque in the same way, and not a value carried through the loop);
+// the row address of factor() and the workgroup kernel's matrix forms use this one.
 __device__ __forceinline__ int opaque_lane(int lane) {
   asm volatile("" : "+v"(lane));
   return lane;
@@ -732,8 +748,8 @@ struct NewtonMatrixGJ64 {
   int permv;  // lane k: the lane whose row was the pivot of step k
 
   template <typename TJ>
-  __device__ __forceinline__ void build(const TJ* J, int ldj, double gamma, int lane_in, int n) {
-    const int lane = opaque_lane(lane_in);
+  __device__ __forceinline__ void build(const TJ* J, int ldj, double gamma, int n) {
+    const int lane = wave_lane();
 #pragma unroll
     for (int j = 0; j < N; ++j)
       a[j] = (j == lane ? 1.0 : 0.0) - gamma * J[j * ldj + lane];  // J rows / columns >= n are zero
@@ -745,8 +761,8 @@ struct NewtonMatrixGJ64 {
   // instead of 2 v_readlane + the SGPR-forwarding wait of a register broadcast (the readlane form,
   // pair by pair inside the elimination loop, measured 1.0 % slower on configs[2]:
   // profiles/r07b_ab_gj_readlane_pivot_row.log).
-  __device__ __forceinline__ bool factor(int lane_in, int n, int orow) {
-    const int lane = opaque_lane(lane_in);
+  __device__ __forceinline__ bool factor(int n, int orow) {
+    const int lane = wave_lane();
     bool pivoted = lane >= N;
     permv = lane;
     bool ok = true;
@@ -771,6 +787,9 @@ struct NewtonMatrixGJ64 {
         // re-packs the row into 4-VGPR tuples for ds_write_b128 (2 v_mov per processed column and
         // step: ~3,000 VALU issues per factorisation at N = 54).  LDS operations of one wave complete
         // in issue order, so the other lanes' ds_read_b128 after wave_lds_sync see these stores.
+        // (ds_write2_b64, two register pairs per instruction, halves the store count and measured
+        // 2.8 % slower on configs[2]: its data transfer takes as long as the two stores it replaces;
+        // profiles/r08_ab_steps.log)
         const uint32_t rb = (uint32_t)(uintptr_t)row;
 #pragma unroll
         for (int j = 0; j < N; ++j)
@@ -816,15 +835,14 @@ struct NewtonMatrixGJ64 {
   }
 
   template <typename TJ>
-  __device__ __forceinline__ bool build_factor(const TJ* J, int ldj, double gamma, int lane, int n, int orow) {
-    build(J, ldj, gamma, lane, n);
-    return factor(lane, n, orow);
+  __device__ __forceinline__ bool build_factor(const TJ* J, int ldj, double gamma, int n, int orow) {
+    build(J, ldj, gamma, n);
+    return factor(n, orow);
   }
 
   // x = M^-1 b (lane k: component k)
-  __device__ __forceinline__ double solve(double b, int lane_in, int n) const {
-    const int lane = opaque_lane(lane_in);
-    if (lane >= n) b = 0.0;
+  __device__ __forceinline__ double solve(double b, int n) const {
+    if (wave_lane() >= n) b = 0.0;
     const double bp = bpermute(permv, b);  // lane j: b[p_j]
     double s0 = 0.0, s1 = 0.0;
 #pragma unroll
@@ -846,17 +864,16 @@ struct NewtonMatrixF32S {
   float a[N];
   int permv;
   template <typename TJ>
-  __device__ __forceinline__ bool build_factor(const TJ* J, int ldj, double gamma, int lane, int n, int orow) {
+  __device__ __forceinline__ bool build_factor(const TJ* J, int ldj, double gamma, int n, int orow) {
     NewtonMatrixGJ64<N> m;
-    const bool ok = m.build_factor(J, ldj, gamma, lane, n, orow);
+    const bool ok = m.build_factor(J, ldj, gamma, n, orow);
 #pragma unroll
     for (int j = 0; j < N; ++j) a[j] = (float)m.a[j];
     permv = m.permv;
     return ok;
   }
-  __device__ __forceinline__ double solve(double b, int lane_in, int n) const {
-    const int lane = opaque_lane(lane_in);
-    if (lane >= n) b = 0.0;
+  __device__ __forceinline__ double solve(double b, int n) const {
+    if (wave_lane() >= n) b = 0.0;
     const double bp = bpermute(permv, b);
     double s0 = 0.0, s1 = 0.0;
 #pragma unroll

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           if (polishing ? (c.nadap < PSR_POLISH_ITERS && res < PSR_POLISH_RATE * c.delp) : res <= PSR_POLISH_MAX) {
             c.nadap = polishing ? c.nadap + 1 : 1;
             c.delp = res;
-            const double d = M.solve(act ? S.gammap * fe : 0.0, lane, n);
+            const double d = M.solve(act ? S.gammap * fe : 0.0, n);
             S.nni++;
             b.y = act ? y_e + d : 0.0;
             REQUEST_F(S.tn, b.y, ST_PSR_POLISH_F);
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
 #endif
           // each lane reads back only the J entries it wrote itself (same-address order); the
           // dwdT row of the slice (free here) is the pivot-row scratch
-          const bool ok = M.build_factor(Jg, WAVE, S.gamma, lane, n, L.base + 32 * VL);
+          const bool ok = M.build_factor(Jg, WAVE, S.gamma, n, L.base + 32 * VL);
 #ifdef CKMI_PHASE_TIMERS
           ph[PH_LU] += __builtin_amdgcn_s_memtime() - t0;
 #endif
@@ -602,7 +602,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
 #ifdef CKMI_PHASE_TIMERS
           const unsigned long long t0 = __builtin_amdgcn_s_memtime();
 #endif
-          double x = M.solve(rhs, lane, n);
+          double x = M.solve(rhs, n);
 #ifdef CKMI_PHASE_TIMERS
           ph[PH_SOLVE] += __builtin_amdgcn_s_memtime() - t0;
 #endif
@@ -996,7 +996,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
 #endif
 #ifdef CKMI_PHASE_TIMERS
     unsigned long long sub[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    fe = reactor_rhs<PL, PF, PSR>(V, R, t_e, y_e, L, oJ, lane, N, with_j, Yin, sub);
+    fe = reactor_rhs<PL, PF, PSR>(V, R, t_e, y_e, L, oJ, N, with_j, Yin, sub);
     ph[with_j ? PH_JAC : PH_RHS] += __builtin_amdgcn_s_memtime() - t0;
     if (!with_j) {
       ph[5] += sub[0];
@@ -1008,7 +1008,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
       }
     }
 #else
-    fe = reactor_rhs<PL, PF, PSR>(V, R, t_e, y_e, L, oJ, lane, N, with_j, Yin);
+    fe = reactor_rhs<PL, PF, PSR>(V, R, t_e, y_e, L, oJ, N, with_j, Yin);
 #endif
   }
 #undef REQUEST_F

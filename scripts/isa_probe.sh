@@ -8,7 +8,7 @@ OUT=${ISA_OUT:-/tmp/ckmi_probe.s}
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -munsafe-fp-atomics -mcode-object-version=5 --offload-arch=gfx950 \
   -mllvm -disable-machine-licm -mllvm -disable-machine-sink -mllvm -pragma-unroll-threshold=2000000 \
   --offload-device-only -S -DCKMI_PROBE_C3 "$@" -o "$OUT" "$ROOT/pychemkin_amd/csrc/ckmi.hip"
-K=_ZN12_GLOBAL__N_114reactor_kernelILi54ELb0ELb0EEEvN4ckmi9MechImageEPKNS1_6DevCfgEiiPiPdNS1_9ReactorIOE
+K=_ZN12_GLOBAL__N_114reactor_kernelILi54ELb0ELb0ELb0EEEvN4ckmi9MechImageEPKNS1_6DevCfgEiiPiPdNSt11conditionalIXT2_ENS1_5PsrIOENS1_9ReactorIOEE4typeE
 for f in num_vgpr numbered_sgpr private_seg_size; do  # (num_vgpr may print nothing when it is an expression)
   grep -m1 "\.set $K\.$f," "$OUT" | sed "s/.*\.$f, /$f /"
 done
