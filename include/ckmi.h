@@ -341,6 +341,45 @@ int ckmi_psr_run(const ckmi_mech* mech, const ckmi_reactor_cfg* cfg, const ckmi_
                  const double* tau_or_vol, const double* Tguess, const double* Yguess, double* Tss, double* Yss,
                  double* rho, double* tau_res, double* vol, double* resid, int32_t* stats, void* stream);
 
+/* Batched gas-phase chemical equilibrium and Chapman-Jouguet detonation states (ideal gas, element
+ * potentials; replaces KINCalculateEquil / KINCalculateEquilWithOption / KINCalculateEqGasWithOption,
+ * chemkin_wrapper.py:513-541, mixture.py:3574-3961, one state per call there).  n independent states per
+ * launch, one option per state (mixture.py:3604-3617):
+ *   1 T and P    2 T and V    3 T and S    4 P and V    5 P and H
+ *   6 P and S    7 V and U    8 V and H    9 V and S   10 Chapman-Jouguet detonation
+ * held at the values of the given state (T, P, Y).  Per gram of mixture the unknowns are ln n_j, ln n, ln T
+ * and ln P; every option is the same damped Newton iteration on the reduced (MM + 3)-row system of the element
+ * balances, the total-moles row and the option's two rows, cold-started.  A state has
+ * converged at an undamped step whose relative corrections are all <= tol.  Option 10 holds V and the Hugoniot
+ * H - (P - P1)(V1 + V) / 2 = H1 of the given state and finds the V / V1 in [cj_vlo, cj_vhi] of the least
+ * detonation speed D = V1 sqrt((P - P1) / (V1 - V)) by a bracketed secant iteration inside the kernel, from
+ * cj_start, until V / V1 moves by <= cj_tol; at most cj_iter Hugoniot points.
+ * Works for any species count; needs the element counts (desc.ncf) of at most CKMI_PROJ_MMAX elements
+ * (CKMI_ERR_UNSUPPORTED otherwise).  A zero cfg field selects its default.  All arrays are device pointers:
+ *   option [n] int32; T [n] K, P [n] dyn/cm2, Y [n][KK] mass fractions          the given states
+ *   Teq, Peq [n], Yeq [n][KK]                                                   the equilibrium states
+ *   sound, detspeed [n]  cm/s: the burnt gas's sound speed D V2 / V1 (the CJ condition) and D; 0 for options 1-9
+ *   stats [n][CKMI_EQ_NSTAT] int32
+ * A state that does not converge within max_iter iterations (per Hugoniot point for option 10), a CJ minimum
+ * on an end of the bracket, an option outside 1..10 or T, P <= 0 gets CKMI_RUN_EQ_NOT_CONVERGED and its last
+ * iterate (the given state if it never started). */
+typedef struct {
+  double tol;       /* convergence tolerance, default 1e-12 */
+  int32_t max_iter; /* Newton iteration cap, default 200 */
+  double cj_vlo, cj_vhi; /* bracket of V / V1, default 0.30, 0.97 */
+  double cj_start;  /* first V / V1, default 0.60 */
+  double cj_tol;    /* default 1e-9 */
+  int32_t cj_iter;  /* Hugoniot points at most, default 40 */
+} ckmi_equil_cfg;
+#define CKMI_EQ_STAT_ITER 0    /* Newton iterations (option 10: over all Hugoniot points) */
+#define CKMI_EQ_STAT_STATUS 1  /* CKMI_RUN_OK or CKMI_RUN_EQ_NOT_CONVERGED */
+#define CKMI_EQ_STAT_CJ_ITER 2 /* Hugoniot points solved (option 10) */
+#define CKMI_EQ_NSTAT 4
+#define CKMI_RUN_EQ_NOT_CONVERGED 7
+int ckmi_equil_run(const ckmi_mech* mech, const ckmi_equil_cfg* cfg, int32_t n, const int32_t* option,
+                   const double* T, const double* P, const double* Y, double* Teq, double* Peq, double* Yeq,
+                   double* sound, double* detspeed, int32_t* stats, void* stream);
+
 /* Heat rates of a single-zone engine run (problem 4) on its saved states, evaluated with the
  * integrator's own right-hand side: the output side of KINAll0D_GetEngineHeatRelease
  * (engine.py:953-988).  T0, P0 and Y0 [KK] (device) are the cylinder's initial state (they fix its

@@ -133,6 +133,11 @@ int KINGetMixtureConductivity(int*, double*, double*, double*);                 
 int KINGetMixtureDiffusionCoeffs(int*, double*, double*, double*, double*);     /* :456-462 */
 int KINGetOrdinaryDiffusionCoeffs(int*, double*, double*, double*, double*);    /* :464-470 */
 int KINGetThermalDiffusionCoeffs(int*, double*, double*, double*, double*, double*); /* :472-479 */
+/* Gas-phase equilibrium (ckmi_equil_run with one state; ideal gas): chemset, [option 1..10, [useRealGas = 0,]]
+ * P [dyn/cm2], T [K], X[KK] mole fractions -> [Peq, Teq, sound speed, detonation speed [cm/s],] Xeq[KK].
+ * KINCalculateEquil is option 1 (T and P held).  KINCalculateEquilWithOption has no output slots for the state:
+ * it writes the equilibrium pressure and temperature back into P and T (the reference never calls it, so
+ * this is this library's reading).  useRealGas = 1 returns CKMI_ERR_UNSUPPORTED. */
 int KINCalculateEquil(int*, double*, double*, double*, double*);                /* :513-519 */
 int KINCalculateEquilWithOption(int*, int*, double*, double*, double*, double*); /* :521-528 */
 int KINCalculateEqGasWithOption(int*, int*, int*, double*, double*, double*, double*, double*, double*,

@@ -6,7 +6,8 @@ and the plug-flow reactors (``pychemkin_amd.flowreactors.PFR``, on the same kern
 batched entry point BatchSweep.  Numerics run in hand-written gfx950 HIP kernels
 (libckmi.so, include/ckmi.h).  Units are cgs as the reference sets with KINSetUnitSystem(1).
 """
-from .batch import BatchPSR, BatchResult, BatchSweep, PSRResult, afactor_sensitivity
+from .batch import (BatchEquilibrium, BatchPSR, BatchResult, BatchSweep, EquilibriumResult, PSRResult,
+                    afactor_sensitivity)
 from .batchreactor import (
     BatchReactors,
     GivenPressureBatchReactor_EnergyConservation,
@@ -30,8 +31,8 @@ from .constants import (
 )
 from .inlet import Stream
 from .logger import logger
-from .mixture import (Mixture, adiabatic_mixing, calculate_mixture_temperature_from_enthalpy, interpolate_mixtures,
-                      isothermal_mixing)
+from .mixture import (Mixture, adiabatic_mixing, calculate_equilibrium, calculate_mixture_temperature_from_enthalpy,
+                      detonation, equilibrium, interpolate_mixtures, isothermal_mixing)
 from .reactormodel import Keyword, Profile
 
 __version__ = "0.1.0"

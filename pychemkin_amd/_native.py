@@ -83,6 +83,17 @@ class PsrCfg(ct.Structure):
 
 RUN_NOT_STEADY = 6  # CKMI_RUN_NOT_STEADY: a PSR reached t_max before the steady-state rule was met
 
+
+class EquilCfg(ct.Structure):
+    """ckmi_equil_cfg: a zero field selects its default (tol 1e-12, max_iter 200, V / V1 in [0.30, 0.97] from
+    0.60, cj_tol 1e-9, cj_iter 40)."""
+    _fields_ = [("tol", ct.c_double), ("max_iter", ct.c_int32), ("cj_vlo", ct.c_double), ("cj_vhi", ct.c_double),
+                ("cj_start", ct.c_double), ("cj_tol", ct.c_double), ("cj_iter", ct.c_int32)]
+
+
+EQ_NSTAT = 4  # CKMI_EQ_NSTAT: iterations, status, Hugoniot points (option 10), reserved
+RUN_EQ_NOT_CONVERGED = 7  # CKMI_RUN_EQ_NOT_CONVERGED
+
 _lib: Optional[ct.CDLL] = None
 
 # every symbol include/ckmi.h declares, with its prototype
@@ -105,6 +116,7 @@ PROTOTYPES = {
     "ckmi_engine_heat_rates": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.c_double, ct.c_double, _P, ct.c_int32, _P, _P,
                                           _P, _P, _P]),
     "ckmi_psr_run": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.POINTER(PsrCfg), ct.c_int32] + [_P] * 15),
+    "ckmi_equil_run": (ct.c_int, [_P, ct.POINTER(EquilCfg), ct.c_int32] + [_P] * 11),
     "ckmi_set_reactor_path": (ct.c_int, [ct.c_int32]),
     "ckmi_big_max_image_bytes": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32]),
     "ckmi_set_rop_path": (ct.c_int, [ct.c_int32]),
@@ -538,6 +550,36 @@ class DeviceMechanism:
         # the inputs stay referenced by the result (the launch is asynchronous on this stream)
         return dict(T=Tss, Y=Yss, rho=rho, tau=tau, vol=vol, resid=resid, stats=stats,
                     _inputs=[P, Tin, Yin, mdot, tv, Tg, Yg])
+
+    def equil_run(self, option, T, P, Y, tol: float = 0.0, max_iter: int = 0, cj_bracket=(0.0, 0.0),
+                  cj_start: float = 0.0, cj_tol: float = 0.0, cj_iter: int = 0):
+        """n chemical-equilibrium (options 1-9) or Chapman-Jouguet (option 10) states in one launch
+        (ckmi_equil_run, include/ckmi.h).  option [n] int32, T [n] K, P [n] dyn/cm2, Y [n][KK] mass fractions;
+        zero tolerances / caps select the defaults.  Returns a dict of device tensors: T, P, Y, sound,
+        detspeed [cm/s], stats [n][EQ_NSTAT] (iterations, status, Hugoniot points)."""
+        if not isinstance(option, torch.Tensor):
+            ov = np.asarray(option)
+            if ov.size and not np.all((ov >= 1) & (ov <= 10)):
+                raise NativeError("the equilibrium option must be 1..10 for every state")
+        T = self._dev(T).reshape(-1)
+        n = T.numel()
+        P = self._dev(P).reshape(-1)
+        opt = self._dev(option, torch.int32).reshape(-1)
+        if P.numel() != n or opt.numel() != n:
+            raise ValueError("option, T and P must all have n entries")
+        Y = self._dev(Y).reshape(n, self.KK)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        Teq, Peq, sound, det = (torch.empty(n, **f64) for _ in range(4))
+        Yeq = torch.empty((n, self.KK), **f64)
+        stats = torch.empty((n, EQ_NSTAT), dtype=torch.int32, device=self.device)
+        cfg = EquilCfg(float(tol), int(max_iter), float(cj_bracket[0]), float(cj_bracket[1]), float(cj_start),
+                       float(cj_tol), int(cj_iter))
+        with torch.cuda.device(self.device):
+            _check(lib().ckmi_equil_run(self._h, ct.byref(cfg), n, _ptr(opt), _ptr(T), _ptr(P), _ptr(Y), _ptr(Teq),
+                                        _ptr(Peq), _ptr(Yeq), _ptr(sound), _ptr(det), _ptr(stats),
+                                        _stream_ptr(self.device)), "ckmi_equil_run")
+        # the inputs stay referenced by the result (the launch is asynchronous on this stream)
+        return dict(T=Teq, P=Peq, Y=Yeq, sound=sound, detspeed=det, stats=stats, _inputs=[opt, T, P, Y])
 
     def engine_heat_rates(self, cfg: ReactorCfg, T0: float, P0: float, Y0, t, y):
         """Apparent heat-release and wall heat-loss rates [erg/s] of an engine run (problem 4) on its

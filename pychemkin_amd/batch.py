@@ -210,13 +210,25 @@ class BatchPSR:
             raise _native.NativeError("the burnt estimate's closed reactors failed: status " + str(r.status.tolist()))
         return r.T[inv], r.Y[inv]
 
+    def equilibrium_estimate(self, Tin, P, Yin):
+        """HP equilibrium (T, Y) of each inlet -- the reference PSR model's own estimate (stirreactors/PSR.py:
+        324,362): one BatchEquilibrium launch over the distinct (Tin, P, Yin) rows."""
+        key = np.concatenate([Tin[:, None], P[:, None], Yin], axis=1)
+        uniq, inv = np.unique(key, axis=0, return_inverse=True)
+        inv = np.asarray(inv).reshape(-1)
+        r = BatchEquilibrium(self.chem, devices=self.devices).run(5, uniq[:, 0], uniq[:, 1], Y=uniq[:, 2:])
+        if np.any(r.status != 0):
+            raise _native.NativeError("the equilibrium estimate did not converge: status " + str(r.status.tolist()))
+        return r.T[inv], r.Y[inv]
+
     def run(self, Tin, P, mdot, tau=None, volume=None, Xin=None, Yin=None, estimate="inlet",
             T_estimate=None, X_estimate=None, Y_estimate=None) -> PSRResult:
         """Solve reactors i = 0..n-1 (every input broadcasts over the reactors).
 
         Tin [K], P [dyn/cm2], mdot [g/s], Xin or Yin: the one effective inlet of each reactor; tau [s] or
         volume [cm3] by the mode.  estimate: "inlet" (the inlet state; T_estimate overrides its
-        temperature), "burnt" (burnt_estimate), or "given" with T_estimate and X_estimate / Y_estimate."""
+        temperature), "burnt" (burnt_estimate), "equilibrium" (equilibrium_estimate: the HP equilibrium of the
+        inlet), or "given" with T_estimate and X_estimate / Y_estimate."""
         import torch
 
         tv = tau if self.mode == 1 else volume
@@ -236,6 +248,8 @@ class BatchPSR:
         Yin = self._fractions(n, Xin, Yin, "inlet")
         if estimate == "burnt":
             Tg, Yg = self.burnt_estimate(P, Yin)
+        elif estimate == "equilibrium":
+            Tg, Yg = self.equilibrium_estimate(Tin, P, Yin)
         elif estimate == "inlet":
             Tg, Yg = Tin.copy(), Yin
             if T_estimate is not None:
@@ -246,7 +260,7 @@ class BatchPSR:
             Tg = np.broadcast_to(np.asarray(T_estimate, dtype=np.float64).reshape(-1), (n,)).copy()
             Yg = self._fractions(n, X_estimate, Y_estimate, "estimate")
         else:
-            raise ValueError('estimate must be "inlet", "burnt" or "given"')
+            raise ValueError('estimate must be "inlet", "burnt", "equilibrium" or "given"')
         devs = self._devices()
         if not devs:
             raise _native.NativeError("no ROCm GPU visible: BatchPSR requires at least one MI355X")
@@ -272,6 +286,82 @@ class BatchPSR:
             out.volume[idx] = res["vol"].cpu().numpy()
             out.resid[idx] = res["resid"].cpu().numpy()
             out.stats[idx] = res["stats"].cpu().numpy()
+        return out
+
+
+@dataclass
+class EquilibriumResult:
+    T: np.ndarray            # equilibrium temperature [K]
+    P: np.ndarray            # equilibrium pressure [dyn/cm2]
+    Y: np.ndarray            # equilibrium mass fractions [n, KK]
+    sound: np.ndarray        # option 10: sound speed of the burnt gas [cm/s] (= D V2 / V1), else 0
+    detspeed: np.ndarray     # option 10: detonation wave speed D [cm/s], else 0
+    iterations: np.ndarray   # Newton iterations
+    status: np.ndarray       # 0 converged, 7 (_native.RUN_EQ_NOT_CONVERGED) not: the state is the last iterate
+    wt: np.ndarray
+
+    @property
+    def X(self) -> np.ndarray:
+        x = self.Y / self.wt
+        return x / x.sum(axis=1, keepdims=True)
+
+
+class BatchEquilibrium:
+    """Many independent chemical-equilibrium and Chapman-Jouguet states in one launch per GPU
+    (include/ckmi.h ckmi_equil_run): flame-temperature maps, equilibrium tables, estimates for PSRs."""
+
+    def __init__(self, chem: Chemistry, devices: Optional[Sequence[int]] = None, tol: float = 0.0, max_iter: int = 0):
+        """tol / max_iter: the Newton tolerance and iteration cap (0: the defaults, 1e-12 and 200)."""
+        self.chem = chem
+        self.devices = list(devices) if devices is not None else None
+        self.tol, self.max_iter = float(tol), int(max_iter)
+
+    _devices = BatchSweep._devices
+    _fractions = BatchPSR._fractions
+
+    def run(self, option, T, P, X=None, Y=None) -> EquilibriumResult:
+        """States i = 0..n-1 from (T[i] K, P[i] dyn/cm2, X[i] or Y[i]) under option[i] (1..10, see
+        mixture.calculate_equilibrium); every input broadcasts over the states."""
+        import torch
+
+        wt = self.chem.WT
+        arrs = [np.asarray(option).reshape(-1), np.asarray(T, dtype=np.float64).reshape(-1),
+                np.asarray(P, dtype=np.float64).reshape(-1)]
+        n = max(a.size for a in arrs)
+        for f in (X, Y):
+            if f is not None and np.ndim(f) == 2:
+                n = max(n, np.shape(f)[0])
+        option, T, P = (np.broadcast_to(a, (n,)).copy() for a in arrs)
+        if np.any(option != option.astype(np.int32)) or np.any((option < 1) | (option > 10)):
+            raise ValueError("option must be an integer 1..10 for every state")
+        if np.any(T <= 0) or np.any(P <= 0):
+            raise ValueError("T and P must be > 0")
+        Yv = self._fractions(n, X, Y, "state")
+        option = option.astype(np.int32)
+        devs = self._devices()
+        if not devs:
+            raise _native.NativeError("no ROCm GPU visible: BatchEquilibrium requires at least one MI355X")
+        shards = [np.arange(r, n, len(devs)) for r in range(len(devs))]
+        pending = []
+        for d, idx in zip(devs, shards):
+            if idx.size == 0:
+                continue
+            dm = self.chem.device_mechanism(d)
+            with torch.cuda.device(d):
+                res = dm.equil_run(option[idx], T[idx], P[idx], Yv[idx], tol=self.tol, max_iter=self.max_iter)
+            pending.append((idx, res))
+        out = EquilibriumResult(T=np.empty(n), P=np.empty(n), Y=np.empty((n, wt.size)), sound=np.empty(n),
+                                detspeed=np.empty(n), iterations=np.empty(n, np.int32), status=np.empty(n, np.int32),
+                                wt=wt)
+        for idx, res in pending:
+            out.T[idx] = res["T"].cpu().numpy()
+            out.P[idx] = res["P"].cpu().numpy()
+            out.Y[idx] = res["Y"].cpu().numpy()
+            out.sound[idx] = res["sound"].cpu().numpy()
+            out.detspeed[idx] = res["detspeed"].cpu().numpy()
+            st = res["stats"].cpu().numpy()
+            out.iterations[idx] = st[:, 0]
+            out.status[idx] = st[:, 1]
         return out
 
 

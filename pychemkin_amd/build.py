@@ -16,6 +16,7 @@ JIT_SRC = os.path.join(HERE, "csrc", "ckmi_jit.cpp")  # mechanism-specialised RO
 PARSE_SRC = os.path.join(HERE, "csrc", "ckmi_parse.cpp")  # native Chemkin-II interpreter (KINPreProcess)
 TRAN_SRC = os.path.join(HERE, "csrc", "ckmi_transport.hip")  # viscosity fits + species / mixture viscosity
 PSR_SRC = os.path.join(HERE, "csrc", "ckmi_psr.hip")  # steady-state PSRs: the open-reactor kernel instantiations
+EQUIL_SRC = os.path.join(HERE, "csrc", "ckmi_equil.hip")  # batched chemical equilibrium and CJ states
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("ckmi_device.hpp", "ckmi_reactor.hpp", "ckmi_image.hpp",
                                                 "ckmi_run.hpp", "ckmi_internal.hpp", "ckmi_reactor_kernel.hpp")] + [
     os.path.join(HERE, "..", "include", "ckmi.h"), os.path.join(HERE, "..", "include", "ckmi_kin.h")]
@@ -51,7 +52,7 @@ def _stale(target: str, sources) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(OUT, [SRC, LU_SRC, BIG_SRC, KIN_SRC, JIT_SRC, PARSE_SRC, TRAN_SRC, PSR_SRC] + DEPS)
+    return _stale(OUT, [SRC, LU_SRC, BIG_SRC, KIN_SRC, JIT_SRC, PARSE_SRC, TRAN_SRC, PSR_SRC, EQUIL_SRC] + DEPS)
 
 
 PROF_OUT = os.path.join(HERE, "_lib", "libckmi_prof.so")  # diagnostic phase-timer build
@@ -68,7 +69,7 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
     """Build libckmi.so (or the phase-timer build, or an A/B variant at `out` with `extra` flags).
 
     Separately compiled translation units (the reactor kernel alone takes ~2 min) linked into one
-    shared library: ckmi.hip, ckmi_psr.hip, ckmi_lu.hip, ckmi_big.hip and the host-only ckmi_kin.cpp,
+    shared library: ckmi.hip, ckmi_psr.hip, ckmi_equil.hip, ckmi_lu.hip, ckmi_big.hip and the host-only ckmi_kin.cpp,
     ckmi_parse.cpp and ckmi_jit.cpp (linked with libhiprtc)."""
     default = out is None and not prof and not extra
     out = out or (PROF_OUT if prof else OUT)
@@ -101,6 +102,10 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
     psr_obj = os.path.join(OBJ_DIR, "ckmi_psr.o")
     if force or _stale(psr_obj, [PSR_SRC] + DEPS):
         jobs.append((PSR_SRC, psr_obj, FLAGS))
+    # the equilibrium kernels: the in-register solve is a fully unrolled loop nest, as the reactor kernel's
+    equil_obj = os.path.join(OBJ_DIR, "ckmi_equil.o")
+    if force or _stale(equil_obj, [EQUIL_SRC] + DEPS):
+        jobs.append((EQUIL_SRC, equil_obj, FLAGS))
     # a variant that only names the workgroup kernel shares the default build's ckmi.hip object
     main_extra = [f for f in extra if "CKMI_BIG" not in f]
     # (a phase-timer build never shares the production object, and vice versa)
@@ -113,7 +118,7 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
         for f in [pool.submit(_compile, s, o, fl, verbose) for s, o, fl in jobs]:
             f.result()
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, main_obj, lu_obj, big_obj, kin_obj, jit_obj,
-           parse_obj, tran_obj, psr_obj,
+           parse_obj, tran_obj, psr_obj, equil_obj,
            "-L/opt/rocm/lib", "-lhiprtc", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)

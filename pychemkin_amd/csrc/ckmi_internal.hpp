@@ -76,6 +76,10 @@ struct ckmi_mech {
   double tguard_lo = 0.0, tguard_hi = 1e300;  // runaway guard: min_k T_low,k / 2, max_k T_high,k
   int npe = 0;  // elements of the corrector's element projection (image element table), 0 = none
   ckmi::JitRop* jit = nullptr;
+  // equilibrium tables (ckmi_equil.hip): [KK][EQ_ROW] built from the image at the first ckmi_equil_run and
+  // owned by allocs; eq_mm = 0 until then
+  const double* eq_tab = nullptr;
+  int eq_mm = 0;
 };
 
 namespace ckmi {

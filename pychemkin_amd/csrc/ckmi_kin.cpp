@@ -1561,9 +1561,78 @@ int KINAll0D_CalculateInput(int* lout, int* chemset, char* lines, int* nlines, i
   return run_reactor(s);
 }
 
+// ---------------------------------------------------------------- equilibrium (ckmi_equil_run, n = 1)
+// One state: mole fractions in and out, P [dyn/cm2] and T [K]; option as mixture.py:3604-3617.
+static int equil_one(const int* chemset, int option, const double* P, const double* T, const double* X, double* Peq,
+                     double* Teq, double* sound, double* det, double* Xeq) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  ChemSet* s = get_set(chemset);
+  if (!s) return fail(CKMI_ERR_ARG, "unknown chemistry set");
+  if (!P || !T || !X || !Xeq) return fail(CKMI_ERR_ARG, "bad argument");
+  if (option < 1 || option > 10) return fail(CKMI_ERR_ARG, "the equilibrium option must be 1..10");
+  if (!(*P > 0.0) || !(*T > 0.0)) return fail(CKMI_ERR_ARG, "pressure and temperature must be > 0");
+  const int KK = s->KK;
+  double sxw = 0.0;
+  for (int k = 0; k < KK; ++k) sxw += std::max(X[k], 0.0) * s->wt[k];
+  if (!(sxw > 0.0)) return fail(CKMI_ERR_ARG, "no composition");
+  // device buffer: T, P, Y[KK] | Teq, Peq, sound, det, Yeq[KK] | option and stats[CKMI_EQ_NSTAT] as int32 (4 doubles)
+  const size_t nd = 2 + (size_t)KK + 4 + KK + 4;
+  int rc = ensure_scratch(s, nd);
+  if (rc) return rc;
+  (void)hipSetDevice(s->device);
+  std::vector<double> in(2 + KK);
+  in[0] = *T;
+  in[1] = *P;
+  for (int k = 0; k < KK; ++k) in[2 + k] = std::max(X[k], 0.0) * s->wt[k] / sxw;
+  double* d = s->dbuf;
+  double* o = d + 2 + KK;
+  int32_t* di = (int32_t*)(o + 4 + KK);  // option, then stats[CKMI_EQ_NSTAT]
+  const int32_t opt = option;
+  if ((rc = hip_ok(hipMemcpy(d, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice), "H2D"))) return rc;
+  if ((rc = hip_ok(hipMemcpy(di, &opt, sizeof(opt), hipMemcpyHostToDevice), "H2D"))) return rc;
+  ckmi_equil_cfg cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  rc = ckmi_equil_run(s->mech, &cfg, 1, di, d, d + 1, d + 2, o, o + 1, o + 4, o + 2, o + 3, di + 1, nullptr);
+  if (rc) return fail(rc, ckmi_last_error());
+  if ((rc = hip_ok(hipDeviceSynchronize(), "equilibrium run"))) return rc;
+  std::vector<double> out(4 + KK);
+  int32_t st[CKMI_EQ_NSTAT];
+  if ((rc = hip_ok(hipMemcpy(out.data(), o, out.size() * sizeof(double), hipMemcpyDeviceToHost), "D2H"))) return rc;
+  if ((rc = hip_ok(hipMemcpy(st, di + 1, sizeof(st), hipMemcpyDeviceToHost), "D2H"))) return rc;
+  if (st[CKMI_EQ_STAT_STATUS] != CKMI_RUN_OK)
+    return fail(CKMI_ERR_ARG, "the equilibrium solver did not converge (option " + std::to_string(option) + ", " +
+                                  std::to_string(st[CKMI_EQ_STAT_ITER]) + " iterations)");
+  double sx = 0.0;
+  for (int k = 0; k < KK; ++k) sx += out[4 + k] / s->wt[k];
+  for (int k = 0; k < KK; ++k) Xeq[k] = out[4 + k] / s->wt[k] / sx;
+  if (Teq) *Teq = out[0];
+  if (Peq) *Peq = out[1];
+  if (sound) *sound = out[2];
+  if (det) *det = out[3];
+  return CKMI_OK;
+}
+
+int KINCalculateEquil(int* chemset, double* P, double* T, double* X, double* Xeq) {
+  return equil_one(chemset, 1, P, T, X, nullptr, nullptr, nullptr, nullptr, Xeq);
+}
+
+int KINCalculateEquilWithOption(int* chemset, int* option, double* P, double* T, double* X, double* Xeq) {
+  if (!option) return fail(CKMI_ERR_ARG, "bad argument");
+  return equil_one(chemset, *option, P, T, X, P, T, nullptr, nullptr, Xeq);  // P and T updated in place
+}
+
+int KINCalculateEqGasWithOption(int* chemset, int* option, int* realgas, double* P, double* T, double* X, double* Peq,
+                                double* Teq, double* sound, double* det, double* Xeq) {
+  if (!option) return fail(CKMI_ERR_ARG, "bad argument");
+  if (realgas && *realgas == 1)
+    return fail(CKMI_ERR_UNSUPPORTED, "KINCalculateEqGasWithOption: the real-gas cubic EOS is not on this path "
+                                      "(useRealGas must be 0)");
+  return equil_one(chemset, *option, P, T, X, Peq, Teq, sound, det, Xeq);
+}
+
 // ---------------------------------------------------------------- declared, out of scope
 // The reference declares these at import (chemkin_wrapper.py:300-867), so a drop-in library must
-// export them; they belong to models outside the batch-reactor path (transport, equilibrium, PSR,
+// export them; they belong to models outside the batch-reactor path (transport, PSR,
 // PFR, engines, flames) and return CKMI_ERR_UNSUPPORTED with a message.
 #define CKMI_OUT_OF_SCOPE(name, what, ...) \
   int name(__VA_ARGS__) { return fail(CKMI_ERR_UNSUPPORTED, #name ": " what " is not on this path"); }
@@ -1571,11 +1640,6 @@ CKMI_OUT_OF_SCOPE(KINGetDiffusionCoeffs, "transport", int*, double*, double*, do
 CKMI_OUT_OF_SCOPE(KINGetMixtureDiffusionCoeffs, "transport", int*, double*, double*, double*, double*)
 CKMI_OUT_OF_SCOPE(KINGetOrdinaryDiffusionCoeffs, "transport", int*, double*, double*, double*, double*)
 CKMI_OUT_OF_SCOPE(KINGetThermalDiffusionCoeffs, "transport", int*, double*, double*, double*, double*, double*)
-CKMI_OUT_OF_SCOPE(KINCalculateEquil, "the equilibrium solver", int*, double*, double*, double*, double*)
-CKMI_OUT_OF_SCOPE(KINCalculateEquilWithOption, "the equilibrium solver", int*, int*, double*, double*, double*,
-                  double*)
-CKMI_OUT_OF_SCOPE(KINCalculateEqGasWithOption, "the equilibrium solver", int*, int*, int*, double*, double*,
-                  double*, double*, double*, double*, double*, double*)
 CKMI_OUT_OF_SCOPE(KINAll0D_SetupPSRReactorInputs, "the PSR model", int*, int*, double*, double*, double*, double*,
                   double*, double*, double*, double*, double*, double*)
 CKMI_OUT_OF_SCOPE(KINAll0D_SetupPSRInletInputs, "the PSR model", int*, int*, int*, double*, double*, double*)

@@ -4,7 +4,9 @@ Drop-in subset of ``Mixture`` used by the batch-reactor path (SURVEY.md section 
 state (temperature, pressure, volume, X, Y), composition conversion and normalisation,
 WTM, RHO, concentration, HML/CPBL, ROP, RxnRates, massROP, volHRR, list_ROP,
 list_reaction_rates, X/Y_by_Equivalence_Ratio, list_composition, validate,
-mixture_viscosity and species_Visc (transport data preprocessed, mixture.py:1860-1977).
+mixture_viscosity and species_Visc (transport data preprocessed, mixture.py:1860-1977), and the
+equilibrium functions (calculate_equilibrium, equilibrium, detonation, Find_Equilibrium; mixture.py:3572-3961)
+on the batched equilibrium kernel (ckmi_equil_run).
 
 Kinetics and mixture thermo go through the GPU kernels (ckmi_rop_thermo,
 ckmi_reaction_rates, ckmi_species_thermo) with a batch of one state, exactly as the
@@ -353,6 +355,15 @@ class Mixture:
         qf, qr = dm.reaction_rates(T, P, Y)
         return qf[:, 0].cpu().numpy(), qr[:, 0].cpu().numpy()
 
+    def Find_Equilibrium(self) -> "Mixture":
+        """The mixture at the TP equilibrium of this one (mixture.py:1569-1597): same temperature and
+        pressure, equilibrium composition."""
+        eq = copy.deepcopy(self)
+        _, y = calculate_equilibrium(self.chemID, p=self.pressure, t=self.temperature, frac=self.Y, wt=self._WT,
+                                     mode_in="mass", mode_out="mass")
+        eq.Y = y
+        return eq
+
     def use_idealgas_law(self) -> None:
         """Ideal-gas law for the mixture properties (mixture.py:2706-2740).  The device path is ideal-gas
         only (real-gas cubic EOS is out of scope), so this is the state every mixture is already in."""
@@ -588,3 +599,72 @@ def adiabatic_mixing(recipe: List[Tuple[Mixture, float]], mode: str) -> Mixture:
     if err != 0:
         raise MixtureError(f"mixture temperature from enthalpy did not converge (error {err})")
     return final
+
+
+# ---------------------------------------------------------------------- equilibrium (mixture.py:3572-3961)
+EQUILIBRIUM_OPTIONS = {1: "T and P", 2: "T and V", 3: "T and S", 4: "P and V", 5: "P and H", 6: "P and S",
+                       7: "V and U", 8: "V and H", 9: "V and S", 10: "Chapman-Jouguet detonation"}
+
+
+def calculate_equilibrium(chemID: int, p: float, t: float, frac, wt, mode_in: str, mode_out: str, EQOption: int = 1,
+                          useRealGas: int = 0) -> Tuple[List[float], np.ndarray]:
+    """Equilibrium state of the mixture (p [dyn/cm2], t [K], frac) under EQOption (mixture.py:3574-3797;
+    KINCalculateEqGasWithOption there, one state of ckmi_equil_run on the GPU here):
+
+        1 T and P    2 T and V    3 T and S    4 P and V    5 P and H
+        6 P and S    7 V and U    8 V and H    9 V and S   10 Chapman-Jouguet detonation
+
+    mode_in / mode_out: 'mass' or 'mole' fractions given / returned.  An EQOption outside 1..10 is read as 1,
+    as the reference reads it.  Returns ([P, T, sound speed, detonation speed] in cgs, fractions); the two
+    speeds are 0 unless EQOption is 10.  The real-gas EOS is out of scope: useRealGas = 1 raises, and so
+    does a state the solver does not converge on (the reference exits)."""
+    from . import _native
+
+    if useRealGas == 1:
+        raise MixtureError("the real-gas cubic EOS is not supported by the equilibrium solver (ideal gas only)")
+    if str(mode_out).lower() not in ("mass", "mole"):
+        raise MixtureError('must specify "mole" or "mass" fractions returned.')
+    chem, y = Mixture._static_state(chemID, p, t, frac, wt, mode_in)
+    opt = int(EQOption) if EQOption in EQUILIBRIUM_OPTIONS else 1
+    dm = chem.device_mechanism()
+    r = dm.equil_run(np.array([opt], np.int32), [float(t)], [float(p)], y.reshape(1, -1))
+    st = r["stats"][0].cpu().numpy()
+    if st[1] != 0:
+        raise MixtureError(f"failed to find the equilibrium state (option {opt}: {EQUILIBRIUM_OPTIONS[opt]}; "
+                           f"{int(st[0])} iterations)")
+    y_eq = r["Y"][0].cpu().numpy()
+    statevars = [float(r["P"][0].item()), float(r["T"][0].item()), float(r["sound"][0].item()),
+                 float(r["detspeed"][0].item())]
+    if mode_out.lower() == "mass":
+        return statevars, y_eq
+    return statevars, Mixture.mass_fraction_to_mole_fraction(y_eq, np.asarray(wt, dtype=np.float64))
+
+
+def _equilibrium_mixture(mixture: Mixture, option: int):
+    if not isinstance(mixture, Mixture):
+        raise MixtureError("the first argument must be a Mixture object.")
+    userealgas = 0 if mixture.EOS == 0 else int(bool(mixture.userealgas))
+    eq = copy.deepcopy(mixture)
+    eqvars, y = calculate_equilibrium(mixture.chemID, p=mixture.pressure, t=mixture.temperature, frac=mixture.Y,
+                                      wt=mixture.WT, mode_in="mass", mode_out="mass", EQOption=option,
+                                      useRealGas=userealgas)
+    eq.Y = y
+    eq.pressure = eqvars[0]
+    eq.temperature = eqvars[1]
+    return eqvars, eq
+
+
+def equilibrium(mixture: Mixture, opt: int = 1) -> Mixture:
+    """The mixture at the equilibrium state of `mixture` (mixture.py:3800-3894).  opt: 1 T and P, 2 T and V,
+    4 P and V, 5 P and H, 7 V and U, 8 V and H; 3, 6, 9 and 10 are not available here, as in the reference
+    (calculate_equilibrium takes them; detonation() is option 10)."""
+    if opt in (3, 6, 9, 10):
+        raise MixtureError(f"equilibrium option {opt} is not available.")
+    return _equilibrium_mixture(mixture, opt)[1]
+
+
+def detonation(mixture: Mixture) -> Tuple[List[float], Mixture]:
+    """Chapman-Jouguet state of `mixture` (mixture.py:3897-3961): ([sound speed, detonation wave speed] in
+    cm/s, the burnt mixture at the CJ pressure and temperature)."""
+    eqvars, eq = _equilibrium_mixture(mixture, 10)
+    return [eqvars[2], eqvars[3]], eq
