@@ -15,7 +15,7 @@ THERM = os.path.join(HERE, "grimech30_thermo.dat")
 N_TRACER = 108  # GRI-3.0 + 108 = 161 species: the configs[4] size (n = KK + 1 = 162)
 
 
-def write_big_mechanism(dirpath=HERE, n_tracer=N_TRACER):
+def write_big_mechanism(dirpath=HERE, n_tracer=N_TRACER, chem=CHEM):
     """A synthetic > 63-species mechanism for the large-mechanism kernels (no ~160-species
     mechanism exists offline; SURVEY 8c: parity for configs[4] is unpinned against the reference).
 
@@ -23,8 +23,10 @@ def write_big_mechanism(dirpath=HERE, n_tracer=N_TRACER):
     the enthalpy offset shifted by 10 K per index, so every exchange has K_c != 1), coupled by
     elementary (AXk + H <=> AXk+1 + H), coefficient-2 (2AXk <=> AXk+1 + AXk-1), third-body (with
     AX and H2O efficiencies) and Troe falloff reactions, so species indices > 63 occur in every
-    reaction type, in efficiency lists and as duplicated slots.  Returns (chem_path, therm_path)."""
-    chem = open(CHEM).read().splitlines()
+    reaction type, in efficiency lists and as duplicated slots.  `chem` is the base mechanism the tracers
+    are appended to: any file with GRI-Mech 3.0's species (data/gri30_plog_chem.inp gives "PLOG GRI + n
+    tracers").  Returns (chem_path, therm_path)."""
+    chem = open(chem).read().splitlines()
     therm = open(THERM).read().splitlines()
     names = [f"AX{k}" for k in range(1, n_tracer + 1)]
     out, in_species = ["! SYNTHETIC test mechanism written by data/make_tracer_mechanism.py: GRI-Mech 3.0",

@@ -1305,6 +1305,9 @@ int ckmi_reactor_run_ex(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, int32_t
   // follows it for them (it pulls and drops the other indices: ~0.1 ms per 65,536 reactors when
   // there are none); the problem array is device memory, so the host cannot tell in advance.
   const int no_pf = SEL_NO_PFR;
+  // the automatic choice lets the FP64-inverse launch of the 64-wide variants also take again what the FP32-inverse
+  // launch failed on (error test, convergence); a forced path (3) keeps the FP32 inverse's own status
+  const int pf_sel = rpath == 0 ? SEL_PFR_RETRY : SEL_PFR;
   if (nvar > 64 || rpath == 1) {
     // the workgroup kernel has no engine model: checked on the host (one synchronous copy of problem[])
     std::vector<int32_t> hp(n);
@@ -1321,7 +1324,7 @@ int ckmi_reactor_run_ex(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, int32_t
 #else
   else if (m->has_plog) {
     rc = f64 ? launch_reactors<64, true, true>(m, n, dc, io, st) : launch_reactors<64, true>(m, n, dc, io, st, no_pf);
-    if (!rc && !f64) rc = launch_reactors<64, true, true>(m, n, dc, io, st, SEL_PFR);
+    if (!rc && !f64) rc = launch_reactors<64, true, true>(m, n, dc, io, st, pf_sel);
   } else if (nvar <= 54) {
     if (f64) rc = launch_reactors<54, false, true>(m, n, dc, io, st);
     else {
@@ -1330,7 +1333,7 @@ int ckmi_reactor_run_ex(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, int32_t
     }
   } else {
     rc = f64 ? launch_reactors<64, false, true>(m, n, dc, io, st) : launch_reactors<64>(m, n, dc, io, st, no_pf);
-    if (!rc && !f64) rc = launch_reactors<64, false, true>(m, n, dc, io, st, SEL_PFR);
+    if (!rc && !f64) rc = launch_reactors<64, false, true>(m, n, dc, io, st, pf_sel);
   }
 #endif
   if (rc) return rc;

@@ -99,8 +99,11 @@ __host__ __device__ constexpr int rwaves(bool f64) { return f64 ? 8 : 12; }
 // Plug flow (problem 3) is compiled into the FP64-inverse variants only (PF = F64): its branches
 // cost the FP32-inverse variant, the configs[2] kernel, 12 B of scratch per lane and 0.5 % of its
 // rate.  sel: 0 integrate every reactor, 1 skip the plug-flow reactors, 2 only those (the host
-// pairs a sel 1 launch of an FP32-inverse variant with a sel 2 launch of an FP64 one).
-enum { SEL_ALL = 0, SEL_NO_PFR = 1, SEL_PFR = 2 };
+// pairs a sel 1 launch of an FP32-inverse variant with a sel 2 launch of an FP64 one), 3 those and the reactors
+// the sel 1 launch before it gave up on with repeated error-test or convergence failures (N = 64 variants only:
+// near equilibrium, at steps of 1e-2 s and more, the FP32-stored inverse of the tracer mechanisms' Newton matrix
+// no longer contracts the iteration; the FP64 one integrates the same reactors, tests/test_gpu_size_variants.py).
+enum { SEL_ALL = 0, SEL_NO_PFR = 1, SEL_PFR = 2, SEL_PFR_RETRY = 3 };
 // PSR: the open well-stirred reactor (problem 5, ckmi_psr_run) instead of the closed ones: every reactor of
 // the launch is a PSR, io is a PsrIO, the wave's slice ends with one more [VL] vector (the inlet mass
 // fractions), and the run ends at the first steady state.  A compile-time flag of three FP64-inverse
@@ -263,6 +266,12 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           else prob = io.problem[r];
           // plug flow (3) and engines (4) run in the FP64-inverse launch
           if (PF ? (sel == SEL_PFR && prob < 3) : prob >= 3) break;  // the other launch's reactor
+          if constexpr (PF && !PSR && N == 64) {
+            if (sel == SEL_PFR_RETRY && prob < 3) {  // its status is final unless the FP32 inverse was the cause
+              const int s32 = io.stats[(size_t)r * CKMI_NSTAT + CKMI_STAT_STATUS];
+              if (s32 != CKMI_RUN_ERRTEST && s32 != CKMI_RUN_CONVFAIL) break;
+            }
+          }
           c.r = r;
           // TPRO runs start at the profile's initial temperature
           const double T0 = (cfg->prof_kind == 1 && cfg->energy == 2 && cfg->nprof > 0) ? cfg->prof_v[0] : io.T0[r];

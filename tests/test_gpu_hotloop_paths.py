@@ -10,12 +10,12 @@ the unpredicated wdot scatter, fexp's three-instruction clamp and the 27-store p
 3. fexp at its edges through the generic ROP kernel.
 """
 import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import CHEM, P_ATM, ROOT, THERM, ch4_air_Y, h2_air_Y
+from conftest import P_ATM, ROOT, THERM, ch4_air_Y, h2_air_Y
+from mechanism_variants import gri_subset_text
 
 pytestmark = pytest.mark.gpu
 
@@ -89,35 +89,11 @@ H2_SPECIES = ("H2", "H", "O", "O2", "OH", "H2O", "HO2", "H2O2", "N2", "AR")
 def h2_subset_text():
     """The H2 / O2 subsystem of GRI-Mech 3.0 (10 species, N = 32 variant) cut from the repository's own file:
     reactions whose species all belong to H2_SPECIES, with their LOW / TROE lines, and third-body
-    efficiencies of other species dropped."""
-    lines = open(CHEM).read().split("\n")
-    i0 = next(i for i, l in enumerate(lines) if l.strip().upper().startswith("REACTIONS"))
-    out = ["ELEMENTS", "O H N AR", "END", "SPECIES", " ".join(H2_SPECIES), "END", lines[i0]]
-    keep = False
-    nrx = 0
-    for l in lines[i0 + 1:]:
-        s = l.split("!")[0].strip()
-        if not s or s.upper() == "END":
-            continue
-        if "=" in s:  # a reaction line
-            eq = s.split()[0]
-            sides = re.split(r"<=>|=>|=", eq.replace("(+M)", ""))
-            sp = [re.sub(r"^\d+", "", x) for side in sides for x in side.split("+")]
-            keep = all(x == "M" or x in H2_SPECIES for x in sp)
-            if keep:
-                out.append(l)
-                nrx += 1
-        elif keep:
-            if re.match(r"\s*(LOW|TROE|SRI|REV|DUP)", l, re.I):
-                out.append(l)
-            else:  # efficiencies: NAME/ value/ pairs
-                pairs = re.findall(r"([^\s/]+)\s*/\s*([^/]+?)\s*/", l)
-                eff = " ".join(f"{n}/{v}/" for n, v in pairs if n in H2_SPECIES)
-                if eff:
-                    out.append(eff)
-    out.append("END")
+    efficiencies of other species dropped (the cutter is tests/mechanism_variants.py gri_subset_text)."""
+    text = gri_subset_text(H2_SPECIES, ("O", "H", "N", "AR"))
+    nrx = sum("=" in l.split("!")[0] for l in text.split("\n"))
     assert nrx >= 20, nrx
-    return "\n".join(out) + "\n"
+    return text
 
 
 def test_small_mechanism_n32(tmp_path):
