@@ -392,6 +392,37 @@ int ckmi_engine_heat_rates(const ckmi_mech* mech, const ckmi_reactor_cfg* cfg, d
                            const double* Y0, int32_t n, const double* t, const double* y, double* ahrr,
                            double* qloss, void* stream);
 
+/* Right-hand side and analytic Jacobian of the reactor kernels at given states.  A diagnostic for tests: it
+ * evaluates the device functions the integrators are compiled from (reactor_rhs of the wave kernel, rhs_big of
+ * the workgroup kernel) once per state, in probe kernels of their own; it does not run the integrators.
+ *   problem [n]                       1..5 per state; problem 5 (open reactor) only for every state of a call
+ *   T0, P0, V0 [n], Y0 [n][KK]        the reactor's initial state, which fixes its context (mass, plug-flow mass
+ *                                     flux, the engine's reference state) as ckmi_reactor_run builds it; for
+ *                                     problem 5: the estimate, the pressure and tau_or_vol as ckmi_psr_run takes them
+ *   t [n], y [n][KK+1]                the evaluation points (T, Y_1..Y_KK); a profile is evaluated on the piece
+ *                                     that contains t
+ *   ext                               optional; only afac_rxn / afac are honoured
+ *   psr                               the inlet of problem 5 (required there, ignored otherwise)
+ *   f [n][KK+1]                       f(t, y)
+ *   J [n][KK+1][KK+1]                 row-major, J[i][j] = d f_i / d y_j; NULL: the plain pass, f only.  The wave
+ *                                     kernel's J is FP64; the workgroup kernel's comes back through the FP32 slot it
+ *                                     parks its Jacobian in.  Plug flow: scaled by rho / G like f.
+ * The kernel and its template parameters are chosen as ckmi_reactor_run / ckmi_psr_run choose them from the
+ * mechanism, the problems, cfg->rtol and ckmi_set_reactor_path.  CKMI_ERR_UNSUPPORTED: problem 4 or 5 with
+ * KK + 1 > 64 (problem 4 also on the forced workgroup path); CKMI_ERR_SIZE: an image the workgroup kernel's LDS
+ * does not hold; CKMI_ERR_ARG: a problem outside 1..5, n < 0, a missing array.  All arrays are device pointers;
+ * the call synchronises the stream once (it reads problem[] on the host). */
+typedef struct {
+  int32_t mode;       /* 1 residence time given, 2 volume given (V0 holds tau_or_vol) */
+  const double* Tin;  /* [n] K */
+  const double* Yin;  /* [n][KK] */
+  const double* mdot; /* [n] g/s */
+} ckmi_rhs_psr;
+int ckmi_reactor_rhs_jac(const ckmi_mech* mech, const ckmi_reactor_cfg* cfg, int32_t n, const int32_t* problem,
+                         const double* T0, const double* P0, const double* V0, const double* Y0, const double* t,
+                         const double* y, const ckmi_reactor_ext* ext, const ckmi_rhs_psr* psr, double* f, double* J,
+                         void* stream);
+
 /* Reactor kernel selection (diagnostic / testing): 0 = automatic (one wave per reactor for KK + 1 <= 64,
  * its Newton inverse stored in FP32 unless rtol < 1e-9; one 4-wave workgroup per reactor above, up to
  * KK + 1 = 192), 1 = the workgroup-per-reactor kernel for every mechanism (lets tests run both

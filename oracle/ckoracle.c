@@ -594,6 +594,20 @@ void cko_rhs_jac(const cko_mech* m, const cko_cfg* cfg, double t, const double* 
   reactor_rhs(&c, t, y, f, J);
 }
 
+void cko_rhs_jac_engine(const cko_mech* m, const cko_cfg* cfg, double t, const double* y, double T0, double P0,
+                        const double* Y0, double* f, double* J) {
+  const int KK = m->KK;
+  const double Wbar0 = mean_wt(m, Y0);
+  double Vstart;
+  engine_volume(cfg->eng, 0.0, &Vstart, NULL);
+  rctx c = {m, cfg, 4, P0 * Wbar0 / (RU * T0), Vstart, P0, T0, 0, 0, t};
+  double cp_R[NMAX], h_RT[NMAX], s_R[NMAX], cpm = 0.0;
+  cko_thermo(m, T0, cp_R, h_RT, s_R);
+  for (int k = 0; k < KK; ++k) cpm += Y0[k] * cp_R[k] / m->wt[k];
+  c.gam0 = cpm / (cpm - 1.0 / Wbar0);
+  reactor_rhs(&c, t, y, f, J);
+}
+
 /* ---------------------------------------------------------- dense LU */
 static int lu_factor(int n, double* A, int* piv) {
   for (int k = 0; k < n; ++k) {

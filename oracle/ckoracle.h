@@ -129,6 +129,11 @@ int cko_reactor_batch_pert(const cko_mech* m, const cko_cfg* cfg, int n, const i
 /* dense analytic Jacobian of the batch-reactor RHS (for tests) */
 void cko_rhs_jac(const cko_mech* m, const cko_cfg* cfg, double t, const double* y, double mass_density0,
                  double V0, double P0, double* f, double* J);
+/* the same for the engine (problem 4), whose context is the cylinder's initial state (T0, P0, Y0), not the
+ * evaluation point: its mass, its volume at t = 0 and the Woschni reference state (T0, gamma of the charge), as
+ * cko_reactor builds them */
+void cko_rhs_jac_engine(const cko_mech* m, const cko_cfg* cfg, double t, const double* y, double T0, double P0,
+                        const double* Y0, double* f, double* J);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,8 @@ class Oracle:
                                              _P, _P, ct.POINTER(Result), ct.c_int]
         L.cko_rhs_jac.argtypes = [ct.POINTER(_Mech), ct.POINTER(_Cfg), ct.c_double, _P, ct.c_double, ct.c_double,
                                   ct.c_double, _P, _P]
+        L.cko_rhs_jac_engine.argtypes = [ct.POINTER(_Mech), ct.POINTER(_Cfg), ct.c_double, _P, ct.c_double, ct.c_double,
+                                         _P, _P, _P]
         self.L = L
 
     # ---------------------------------------------------------------- thermo / rop
@@ -263,4 +265,17 @@ class Oracle:
             Y = y[1:]
             rho0 = P0 / (8.31447247e7 * y[0]) / np.sum(Y / self.wt)
         self.L.cko_rhs_jac(ct.byref(self._mech), ct.byref(c), t, _ptr(y), rho0, V0, P0, _ptr(f), _ptr(J))
+        return f, J
+
+    def rhs_jac_engine(self, y, T0, P0, Y0, t=0.0, energy=1, **cfg):
+        """f and J of the engine (problem 4) at (t, y) for the cylinder whose initial state is (T0, P0, Y0)."""
+        c, keep = self.make_cfg(problem=4, energy=energy, **cfg)
+        y = np.ascontiguousarray(y, np.float64)
+        Y0 = np.ascontiguousarray(Y0, np.float64)
+        n = self.KK + 1
+        f = np.zeros(n)
+        J = np.zeros((n, n))
+        self.L.cko_rhs_jac_engine(ct.byref(self._mech), ct.byref(c), t, _ptr(y), float(T0), float(P0), _ptr(Y0),
+                                  _ptr(f), _ptr(J))
+        del keep
         return f, J

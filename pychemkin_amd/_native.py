@@ -81,6 +81,11 @@ class PsrCfg(ct.Structure):
     _fields_ = [("mode", ct.c_int32), ("ss_rtol", ct.c_double), ("ss_atol", ct.c_double)]
 
 
+class RhsPsr(ct.Structure):
+    """ckmi_rhs_psr: the inlet of problem-5 states of ckmi_reactor_rhs_jac."""
+    _fields_ = [("mode", ct.c_int32), ("Tin", _P), ("Yin", _P), ("mdot", _P)]
+
+
 RUN_NOT_STEADY = 6  # CKMI_RUN_NOT_STEADY: a PSR reached t_max before the steady-state rule was met
 
 
@@ -116,6 +121,8 @@ PROTOTYPES = {
     "ckmi_engine_heat_rates": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.c_double, ct.c_double, _P, ct.c_int32, _P, _P,
                                           _P, _P, _P]),
     "ckmi_psr_run": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.POINTER(PsrCfg), ct.c_int32] + [_P] * 15),
+    "ckmi_reactor_rhs_jac": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.c_int32] + [_P] * 7 +
+                             [ct.POINTER(ReactorExt), ct.POINTER(RhsPsr), _P, _P, _P]),
     "ckmi_equil_run": (ct.c_int, [_P, ct.POINTER(EquilCfg), ct.c_int32] + [_P] * 11),
     "ckmi_set_reactor_path": (ct.c_int, [ct.c_int32]),
     "ckmi_big_max_image_bytes": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32]),
@@ -580,6 +587,50 @@ class DeviceMechanism:
                                         _stream_ptr(self.device)), "ckmi_equil_run")
         # the inputs stay referenced by the result (the launch is asynchronous on this stream)
         return dict(T=Teq, P=Peq, Y=Yeq, sound=sound, detspeed=det, stats=stats, _inputs=[opt, T, P, Y])
+
+    def rhs_jac(self, cfg: ReactorCfg, problem, T0, P0, V0, Y0, t, y, jac: bool = True, afac_rxn=None, afac=None,
+                psr=None, out=None):
+        """The reactor kernels' own f(t, y) and analytic Jacobian at n given states (ckmi_reactor_rhs_jac, a
+        diagnostic).  T0, P0, V0 [n], Y0 [n][KK]: the initial state that fixes each reactor's context; t [n],
+        y [n][KK+1] the evaluation points.  psr = (mode, Tin, Yin, mdot) for problem 5 (V0 = tau_or_vol).
+        Returns (f [n][KK+1], J [n][KK+1][KK+1] or None if jac is False); out = (f, J) supplies the tensors."""
+        t = self._dev(t).reshape(-1)
+        n = t.numel()
+        nv = self.KK + 1
+        T0, P0, V0 = (self._dev(v).reshape(-1) for v in (T0, P0, V0))
+        Y0 = self._dev(Y0).reshape(n, self.KK)
+        y = self._dev(y).reshape(n, nv)
+        prob = self._dev(problem, torch.int32).reshape(-1)
+        if not (T0.numel() == P0.numel() == V0.numel() == prob.numel() == n):
+            raise ValueError("problem, T0, P0, V0 and t must all have n entries")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        f = out[0] if out is not None else torch.empty((n, nv), **f64)
+        J = (out[1] if out is not None else torch.empty((n, nv, nv), **f64)) if jac else None
+        ext = ReactorExt()
+        keep = [prob, T0, P0, V0, Y0, t, y]
+        if afac_rxn is not None:
+            ar = self._dev(afac_rxn, torch.int32).reshape(-1)
+            af = self._dev(afac).reshape(-1)
+            if ar.numel() != n or af.numel() != n:
+                raise ValueError("afac_rxn and afac must have n entries")
+            ext.afac_rxn, ext.afac = _ptr(ar), _ptr(af)
+            keep += [ar, af]
+        pc = None
+        if psr is not None:
+            Tin, mdot = (self._dev(v).reshape(-1) for v in (psr[1], psr[3]))
+            Yin = self._dev(psr[2]).reshape(n, self.KK)
+            if Tin.numel() != n or mdot.numel() != n:
+                raise ValueError("Tin and mdot must have n entries")
+            pc = RhsPsr(int(psr[0]), _ptr(Tin), _ptr(Yin), _ptr(mdot))
+            keep += [Tin, Yin, mdot]
+        with torch.cuda.device(self.device):
+            _check(lib().ckmi_reactor_rhs_jac(self._h, ct.byref(cfg), n, _ptr(prob), _ptr(T0), _ptr(P0), _ptr(V0),
+                                              _ptr(Y0), _ptr(t), _ptr(y), ct.byref(ext),
+                                              ct.byref(pc) if pc is not None else None, _ptr(f), _ptr(J),
+                                              _stream_ptr(self.device)), "ckmi_reactor_rhs_jac")
+        torch.cuda.synchronize(self.device)  # a diagnostic call: the inputs may go once it returns
+        del keep
+        return f, J
 
     def engine_heat_rates(self, cfg: ReactorCfg, T0: float, P0: float, Y0, t, y):
         """Apparent heat-release and wall heat-loss rates [erg/s] of an engine run (problem 4) on its

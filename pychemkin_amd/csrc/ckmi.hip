@@ -1379,6 +1379,80 @@ int ckmi_engine_heat_rates(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, doub
   return rc;
 }
 
+int ckmi_reactor_rhs_jac(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, int32_t n, const int32_t* problem,
+                         const double* T0, const double* P0, const double* V0, const double* Y0, const double* t,
+                         const double* y, const ckmi_reactor_ext* ext, const ckmi_rhs_psr* psr, double* f, double* J,
+                         void* stream) {
+  if (!m || !cfg || n < 0) return fail(CKMI_ERR_ARG, "bad argument");
+  if (n > 0 && (!problem || !T0 || !P0 || !V0 || !Y0 || !t || !y || !f))
+    return fail(CKMI_ERR_ARG, "problem, T0, P0, V0, Y0, t, y and f are required");
+  if (cfg->energy != 1 && cfg->energy != 2) return fail(CKMI_ERR_ARG, "energy must be 1 or 2");
+  if (cfg->nprof < 0 || cfg->nprof > 64 || cfg->nprof2 < 0 || cfg->nprof2 > 64 || cfg->nprof3 < 0 || cfg->nprof3 > 64)
+    return fail(CKMI_ERR_ARG, "nprof, nprof2, nprof3 must be in [0, 64]");
+  if (cfg->prof_kind != 0 && cfg->prof_kind != 1) return fail(CKMI_ERR_ARG, "prof_kind must be 0 (VPRO/PPRO) or 1 (TPRO)");
+  if (cfg->prof_kind == 1 && cfg->energy != 2) return fail(CKMI_ERR_ARG, "TPRO needs a given-temperature run (energy = 2)");
+  if (cfg->nprof2 > 0 && cfg->prof2_kind != 1 && cfg->prof2_kind != 2)
+    return fail(CKMI_ERR_ARG, "prof2_kind must be 1 (QPRO) or 2 (AEXT)");
+  if (cfg->nprof2 > 0 && cfg->energy != 1) return fail(CKMI_ERR_ARG, "QPRO / AEXT need an energy-equation run");
+  if (cfg->nprof3 > 0 && !(cfg->nprof2 > 0 && cfg->prof2_kind == 1))
+    return fail(CKMI_ERR_ARG, "the third profile (AEXT) needs a QPRO second profile");
+  if (!(cfg->gfac >= 0.0)) return fail(CKMI_ERR_ARG, "GFAC must be >= 0");
+  if (!(cfg->htc >= 0.0) || !(cfg->areaq >= 0.0) || !(cfg->tamb > 0.0 || cfg->htc * cfg->areaq == 0.0))
+    return fail(CKMI_ERR_ARG, "HTC, AREAQ must be >= 0 and TAMB > 0");
+  if (ext && (ext->afac_rxn != nullptr) != (ext->afac != nullptr)) return fail(CKMI_ERR_ARG, "afac_rxn and afac go together");
+  if (n == 0) return CKMI_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  // the problems decide the kernel: checked on the host (one synchronous copy; a diagnostic call)
+  std::vector<int32_t> hp(n);
+  HIP_CHECK(hipMemcpyAsync(hp.data(), problem, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  int n_lo = 0, n_pf = 0, n_eng = 0, n_psr = 0;
+  for (int32_t p : hp) {
+    if (p < 1 || p > 5) return fail(CKMI_ERR_ARG, "problem must be 1..5 for every state");
+    n_lo += p <= 2, n_pf += p == 3, n_eng += p == 4, n_psr += p == 5;
+  }
+  if (n_psr && n_psr != n) return fail(CKMI_ERR_ARG, "open reactors (problem 5) cannot share a call with closed ones");
+  const int nvar = m->KK + 1;
+  const int rpath = g_reactor_path.load();
+  if ((n_eng || n_psr) && nvar > WAVE)
+    return fail(CKMI_ERR_UNSUPPORTED, "engine and open reactors (problems 4, 5) need KK + 1 <= 64");
+  if (n_eng && rpath == 1)
+    return fail(CKMI_ERR_UNSUPPORTED, "engine reactors (problem 4) need the wave-per-reactor kernel");
+  if (n_eng && cfg->eng[CKMI_ENG_HTMODEL] == 1.0 && !cfg->tran)
+    return fail(CKMI_ERR_ARG, "the engine's ICHX heat transfer needs the transport fits (cfg->tran)");
+  if (n_psr) {
+    if (!psr || (psr->mode != 1 && psr->mode != 2) || !psr->Tin || !psr->Yin || !psr->mdot)
+      return fail(CKMI_ERR_ARG, "problem 5 needs the inlet block: mode 1 or 2, Tin, Yin, mdot");
+    if (cfg->nprof != 0 || cfg->nprof2 != 0 || cfg->nprof3 != 0) return fail(CKMI_ERR_ARG, "profiles do not apply to a PSR");
+  }
+  DevCfg dc;
+  dc.c = *cfg;
+  if (dc.c.gfac == 0.0) dc.c.gfac = 1.0;
+  dc.ncrit = 0;
+  dc.guard_y = std::max(1e-3, 1e3 * cfg->atol);
+  dc.guard_tlo = m->tguard_lo;
+  dc.guard_thi = m->tguard_hi;
+  dc.npe = 0;  // (no integration)
+  ProbeIO io{problem, T0, P0, V0, Y0, t, y, ext ? ext->afac_rxn : nullptr, ext ? ext->afac : nullptr,
+             psr ? psr->Tin : nullptr, psr ? psr->Yin : nullptr, psr ? psr->mdot : nullptr, psr ? psr->mode : 0, f, J};
+  if (n_psr) return launch_psr_probe(m, n, dc, io, st);
+  if (nvar > WAVE || rpath == 1) return launch_big_probe(m, n, dc, io, st);
+  // the template parameters ckmi_reactor_run_ex picks: problems 1 and 2 in the FP32-inverse variant (PF = false,
+  // N = 32 / 54 / 64) unless the FP64 inverse is selected, plug flow and engines in the FP64-inverse one (PF = true)
+  const bool f64 = rpath == 2 || (rpath != 3 && (cfg->rtol < 1e-9 || m->has_general));
+  const int n_hi = n_pf + n_eng;
+  int rc = CKMI_OK;
+  if (m->has_plog) {
+    if (!f64 && n_lo) rc = launch_rhs_probe<true, false, false>(m, n, dc, io, SEL_NO_PFR, 64, st);
+    if (!rc && (f64 || n_hi)) rc = launch_rhs_probe<true, true, false>(m, n, dc, io, f64 ? SEL_ALL : SEL_PFR, 64, st);
+  } else {
+    const int n64 = nvar <= 54 ? 54 : 64;
+    if (!f64 && n_lo) rc = launch_rhs_probe<false, false, false>(m, n, dc, io, SEL_NO_PFR, nvar <= 32 ? 32 : n64, st);
+    if (!rc && (f64 || n_hi)) rc = launch_rhs_probe<false, true, false>(m, n, dc, io, f64 ? SEL_ALL : SEL_PFR, n64, st);
+  }
+  return rc;
+}
+
 int ckmi_set_reactor_path(int32_t path) {
   if (path < 0 || path > 3)
     return fail(CKMI_ERR_ARG, "reactor path must be 0 (automatic), 1 (workgroup), 2 (wave, FP64 inverse) or 3 (wave, "

@@ -365,7 +365,9 @@ __device__ __forceinline__ double rhs_big(const MechView& V, const RunCtx& R, co
     rho = R.rho0 * R.V0 / V_;
     P = rho * RU * T / Wbar;
   }
-  const float jsx = R.pfr ? (float)(rho / R.G) : 1.0f;  // plug flow: d/dx = (rho / G) d/dt
+  // plug flow: d/dx = (rho / G) d/dt.  Applied in FP64, so that a parked entry carries one FP32 rounding (the
+  // cast); an FP32 factor cost two more, its own and the product's (tests/test_gpu_jacobian.py)
+  const double jsx = R.pfr ? rho / R.G : 1.0;
   const double lnT = log(T), invT = 1.0 / T, lnPRT = LN_PATM_RU - lnT;
   double* C = lds_at<double>(L.C);
   double* gRT = lds_at<double>(L.gRT);
@@ -483,12 +485,12 @@ __device__ __forceinline__ double rhs_big(const MechView& V, const RunCtx& R, co
   const double dws = isp ? ((dw0[s] + dw0[KKp + s]) + (dw0[2 * KKp + s] + dw0[3 * KKp + s])) : 0.0;
   const double JkT = isp ? dws * Wk * rinv + (conp ? fY * invT : 0.0) : 0.0;
   if (isp) {
-    Jg[jslot(tid, 0, NB)] = (float)JkT * jsx;
+    Jg[jslot(tid, 0, NB)] = (float)(JkT * jsx);
     lds_at<double>(L.ek)[s] = ekv;
   }
   if (R.energy == 1) {
     const double s2 = bsum(B, ck * fY + ekv * JkT, wid, lane);  // also orders the ek writes
-    if (tid == 0) Jg[0] = (float)(-s2 / cpm - q1 / mcp) * jsx;
+    if (tid == 0) Jg[0] = (float)((-s2 / cpm - q1 / mcp) * jsx);
   } else {
     if (tid == 0) Jg[0] = 0.0f;
     __syncthreads();
@@ -560,10 +562,10 @@ __device__ __forceinline__ double rhs_big(const MechView& V, const RunCtx& R, co
         const int ti = rem & 15, m = rem >> 4, s = col & 15;
         const double* jc = jb + cl * LDJ + ti + 64 * m;
         float4 v;
-        v.x = (float)jc[0] * jsx;
-        v.y = (float)jc[16] * jsx;
-        v.z = (float)jc[32] * jsx;
-        v.w = (float)jc[48] * jsx;
+        v.x = (float)(jc[0] * jsx);
+        v.y = (float)(jc[16] * jsx);
+        v.z = (float)(jc[32] * jsx);
+        v.w = (float)(jc[48] * jsx);
         Jg4[((col >> 4) * NM + m) * NT + ((s >> 2) << 6) + ti + ((s & 3) << 4)] = v;
       }
     }
@@ -1456,7 +1458,135 @@ int launch_big_nc(const ckmi_mech* m, int n, const DevCfg& dc, const ReactorIO& 
   return CKMI_OK;
 }
 
+// ------------------------------------------------------------------ RHS / Jacobian probe (diagnostic)
+// ckmi_reactor_rhs_jac on the workgroup kernel: one workgroup per state makes one rhs_big<PL> call with the
+// context built as ST_NEXT of big_reactor_kernel builds it, in the same LDS layout, and on a with_j call reads
+// the Jacobian back from the parked FP32 slot through jslot(), the index map the Newton-matrix build uses (the
+// plug-flow rho / G factor stays in).  The probe holds its own inlined copy of rhs_big: it checks the source
+// the integrator is compiled from, not its machine code.
+template <bool PL>
+__global__ __launch_bounds__(NT, 1) void big_rhs_probe_kernel(MechImage img, BigLds L, const DevCfg* __restrict__ dcfg,
+                                                             int nstate, int NB, float* __restrict__ jws,
+                                                             double* __restrict__ dws, ProbeIO io) {
+  const ckmi_reactor_cfg* __restrict__ cfg = &dcfg->c;
+  stage_image(0, img);
+  const MechView V = make_view(0, img);
+  const int tid = threadIdx.x;
+  const int wid = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int lane = tid % WAVE;
+  RunCtx& R = *lds_at<RunCtx>(L.ctl + wid * CTL_BYTES + align16((int)sizeof(BdfS)) + align16((int)sizeof(Ctl)) +
+                              align16((int)sizeof(Ign)));
+  float* Jg = jws + (size_t)blockIdx.x * jslot_floats(NB);
+  double* Dg = dws + (size_t)blockIdx.x * NDQ * img.IIp;
+  const int KK = V.KK;
+  const int n = KK + 1;
+  const bool isp = tid >= 1 && tid <= KK;
+  const bool with_j = io.J != nullptr;
+  Blk B;
+  B.ored = L.red;
+  B.phase = 0;
+  for (int i = blockIdx.x; i < nstate; i += gridDim.x) {
+    const int prob = io.problem[i];
+    const double T0 = (cfg->prof_kind == 1 && cfg->energy == 2 && cfg->nprof > 0) ? cfg->prof_v[0] : io.T0[i];
+    const double P0 = io.P0[i];
+    double y0 = 0.0;
+    if (tid == 0) y0 = T0;
+    if (isp) y0 = io.Y0[(size_t)i * KK + tid - 1];
+    const double Wbar0 = 1.0 / bsum(B, isp ? y0 * V.rwt()[tid - 1] : 0.0, wid, lane);
+    const double t = io.t[i];
+    // every wave keeps its own copy of the context, as in big_reactor_kernel
+    R.cfg = cfg;
+    R.pfr = (prob == 3);
+    R.conp = (prob == 1 || prob == 3);
+    R.energy = cfg->energy;
+    R.npv = cfg->prof_kind == 0 ? cfg->nprof : 0;
+    R.ntp = (cfg->prof_kind == 1 && cfg->energy == 2) ? cfg->nprof : 0;
+    R.rho0 = P0 * Wbar0 / (RU * T0);
+    R.V0 = (!R.conp && R.npv > 0) ? cfg->prof_v[0] : io.V0[i];
+    R.P0 = (R.conp && R.npv > 0) ? cfg->prof_v[0] : P0;
+    R.mass = R.rho0 * R.V0;
+    R.G = R.Pm = 0.0;
+    if (R.pfr) {
+      R.G = R.rho0 * R.V0;
+      R.Pm = R.P0 + R.G * R.V0;
+    }
+    R.gfac = cfg->gfac;
+    R.qloss = cfg->qloss;
+    R.htc = cfg->htc;
+    R.areaq = cfg->areaq;
+    R.tamb = cfg->tamb;
+    R.nq = cfg->prof2_kind == 1 ? cfg->nprof2 : 0;
+    R.na = cfg->prof2_kind == 2 ? cfg->nprof2 : cfg->nprof3;
+    R.a_t = cfg->prof2_kind == 2 ? cfg->prof2_t : cfg->prof3_t;
+    R.a_v = cfg->prof2_kind == 2 ? cfg->prof2_v : cfg->prof3_v;
+    {
+      const int ar = io.afac_rxn ? io.afac_rxn[i] : -1;
+      R.pslot = (ar >= 0 && ar < img.II) ? img.slot_of[ar] : -1;
+      R.plnf = R.pslot >= 0 ? log(io.afac[i]) : 0.0;
+    }
+    R.tsel = t;  // the profile piece that contains the evaluation point
+    // the slot starts every state as NaN: an entry below n that the pass fails to write reads back as NaN, not as
+    // the state before's value
+    if (with_j)
+      for (int idx = tid; idx < jslot_floats(NB); idx += NT) Jg[idx] = __builtin_nanf("");
+    __syncthreads();
+    const double yl = tid < n ? io.y[(size_t)i * n + tid] : 0.0;
+    const double fl = rhs_big<PL>(V, R, L, B, t, yl, tid, wid, lane, n, NB, with_j, Jg, Dg, img.jcol_ptr, img.jcol_ent);
+    if (tid < n) io.f[(size_t)i * n + tid] = fl;
+    if (with_j) {
+      __syncthreads();  // the slot's last chunks are written (rhs_big ends on a barrier as well)
+      double* Jo = io.J + (size_t)i * n * n;
+      if (tid < n)  // thread = column
+        for (int r = 0; r < n; ++r) Jo[(size_t)r * n + tid] = (double)Jg[jslot(r, tid, NB)];
+    }
+    __syncthreads();  // the context, the LDS vectors and the slot are rewritten for the next state
+  }
+}
+
+template <bool PL>
+int launch_big_probe_nb(const ckmi_mech* m, int n, int NB, const DevCfg& dc, const ProbeIO& io, hipStream_t stream) {
+  int lds_max = 0;
+  BIG_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
+  const BigLds L = big_layout(m->img.bytes, m->img.KKp, m->img.G, 16 * NB, lds_max);
+  if (L.jcb < BW || L.bytes > lds_max)  // the capacity check of launch_big_nc
+    return set_error(CKMI_ERR_SIZE, "mechanism image too large for the workgroup-per-reactor kernel's LDS (" +
+                                        std::to_string(m->img.bytes) + " B image)");
+  const void* fn = (const void*)big_rhs_probe_kernel<PL>;
+  BIG_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, L.bytes));
+  const int grid = std::min(n, PROBE_GRID_MAX);
+  const size_t jbytes = ((size_t)grid * jslot_floats(NB) * sizeof(float) + 255) & ~(size_t)255;
+  const size_t dbytes = ((size_t)grid * NDQ * m->img.IIp * sizeof(double) + 255) & ~(size_t)255;
+  const size_t cbytes = (sizeof(DevCfg) + 255) & ~(size_t)255;
+  void* ws = nullptr;
+  BIG_CHECK(hipMallocAsync(&ws, jbytes + dbytes + cbytes, stream));
+  char* base = (char*)ws;
+  DevCfg* dcfg = (DevCfg*)(base + jbytes + dbytes);
+  auto* hc = new DevCfg(dc);
+  hipError_t e = hipMemcpyAsync(dcfg, hc, sizeof(DevCfg), hipMemcpyHostToDevice, stream);
+  if (e != hipSuccess) {
+    delete hc;
+    (void)hipFreeAsync(ws, stream);
+    return set_error(CKMI_ERR_HIP, std::string("cfg copy: ") + hipGetErrorString(e));
+  }
+  BIG_CHECK(hipLaunchHostFunc(stream, [](void* p) { delete static_cast<DevCfg*>(p); }, hc));
+  hipLaunchKernelGGL((big_rhs_probe_kernel<PL>), dim3(grid), dim3(NT), L.bytes, stream, m->img, L, dcfg, n, NB,
+                     (float*)base, (double*)(base + jbytes), io);
+  BIG_CHECK(hipGetLastError());
+  BIG_CHECK(hipFreeAsync(ws, stream));
+  return CKMI_OK;
+}
+
 }  // namespace
+
+// the NB and PL launch_big_reactors picks for the mechanism
+int launch_big_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream) {
+  const int nvar = m->KK + 1;
+  if (nvar > BIG_NMAX)
+    return set_error(CKMI_ERR_UNSUPPORTED, "batch reactors with more than " + std::to_string(BIG_NMAX - 1) +
+                                               " species are not supported (the ROP/thermo kernels are)");
+  if (m->has_plog) return launch_big_probe_nb<true>(m, n, nvar <= 128 ? 8 : (nvar <= 176 ? 11 : 12), dc, io, stream);
+  return launch_big_probe_nb<false>(m, n, std::min(12, std::max(4, (nvar + 15) / 16)), dc, io, stream);
+}
 
 int launch_big_reactors(const ckmi_mech* m, int n, const DevCfg& dc, const ReactorIO& io, hipStream_t stream) {
   const int nvar = m->KK + 1;

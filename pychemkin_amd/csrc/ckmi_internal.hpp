@@ -89,4 +89,9 @@ struct ReactorIO;
 int set_error(int code, const std::string& msg);
 // one workgroup per reactor: 64 <= KK + 1 <= 192 (ckmi_big.hip)
 int launch_big_reactors(const ckmi_mech* m, int n, const DevCfg& dc, const ReactorIO& io, hipStream_t stream);
+// RHS / Jacobian probes of ckmi_reactor_rhs_jac: the workgroup kernel's (ckmi_big.hip) and the open-reactor
+// instantiation of the wave kernel's (ckmi_psr.hip)
+struct ProbeIO;
+int launch_big_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream);
+int launch_psr_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream);
 }  // namespace ckmi

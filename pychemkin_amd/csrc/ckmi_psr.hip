@@ -7,6 +7,13 @@ using namespace ckmi;
 #define HIP_CHECK(x) CKMI_RK_HIP_CHECK(x)
 static int fail(int code, const std::string& msg) { return ckmi::set_error(code, msg); }
 
+// ckmi_reactor_rhs_jac on open reactors: the PSR = true instantiation ckmi_psr_run would pick
+int ckmi::launch_psr_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream) {
+  const int nvar = m->KK + 1;
+  if (m->has_plog) return launch_rhs_probe<true, true, true>(m, n, dc, io, SEL_ALL, 64, stream);
+  return launch_rhs_probe<false, true, true>(m, n, dc, io, SEL_ALL, nvar <= 54 ? 54 : 64, stream);
+}
+
 extern "C" {
 
 int ckmi_psr_run(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, const ckmi_psr_cfg* psr, int32_t n, const double* P,

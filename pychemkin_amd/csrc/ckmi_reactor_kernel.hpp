@@ -1081,4 +1081,146 @@ int launch_reactors(const ckmi_mech* m, int n, const DevCfg& dc, const std::cond
   return rc;
 }
 
+// ---------------------------------------------------------------- RHS / Jacobian probe (diagnostic)
+// ckmi_reactor_rhs_jac: one wave per state evaluates the integrator's own reactor_rhs<PL, PF, PSR> once, with
+// the per-reactor context built from the state's initial condition exactly as ST_NEXT of reactor_kernel builds
+// it (engine_heat_kernel of ckmi.hip is the model), and copies f and, on a with_j call, the FP64 Jacobian out
+// of the shared scratch Jsh[col * LDJ + row] into J[row][col].  The probe holds its own inlined copy of
+// reactor_rhs: it checks the source the integrators are compiled from, not their machine code.
+// sel as reactor_kernel: the PF = false instantiation takes problems 1 and 2, the PF = true one the others
+// (SEL_PFR) or every state (SEL_ALL); ncol is the N of the reactor_kernel variant the run would use.
+template <bool PL, bool PF, bool PSR>
+__global__ __launch_bounds__(WAVE) void rhs_probe_kernel(MechImage img, const DevCfg* __restrict__ dcfg, int n, int sel,
+                                                         int ncol, ProbeIO io) {
+  const ckmi_reactor_cfg* __restrict__ cfg = &dcfg->c;
+  stage_image(0, img);
+  const MechView V = make_view(0, img);
+  const int lane = threadIdx.x;
+  const int oJ = img.bytes;
+  WaveLds L;
+  L.base = oJ + align16(8 * ncol * LDJ);
+  RunCtx& R = *lds_at<RunCtx>(L.base + slice_vec_bytes(img.G));
+  double* const Yin = PSR ? lds_at<double>(L.base + slice_vec_bytes(img.G) + align16((int)sizeof(RunCtx))) : nullptr;
+  const int KK = V.KK;
+  const int nv = KK + 1;
+  const bool isp = lane >= 1 && lane <= KK;
+  const int s = isp ? lane - 1 : 0;
+  const double rw = isp ? V.rwt()[s] : 0.0;
+  const bool with_j = io.J != nullptr;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    int prob;
+    if constexpr (PSR) prob = 5;
+    else prob = io.problem[i];
+    if (PF ? (sel == SEL_PFR && prob < 3) : prob >= 3) continue;  // the other launch's state
+    const double T0 = (cfg->prof_kind == 1 && cfg->energy == 2 && cfg->nprof > 0) ? cfg->prof_v[0] : io.T0[i];
+    const double P0 = io.P0[i];
+    const double y0 = lane == 0 ? T0 : (isp ? io.Y0[(size_t)i * KK + s] : 0.0);
+    const double Wbar0 = 1.0 / wave_sum(isp ? y0 * rw : 0.0);
+    double gam0 = 0.0, hin = 0.0;
+    if constexpr (PF && !PSR) {
+      if (prob == 4) {  // engine: gamma of the initial charge
+        const double cpR = isp ? nasa7_img(V, s, T0, log(T0), 1.0 / T0).cpR : 0.0;
+        const double cpm = wave_sum(isp ? y0 * cpR * rw : 0.0);
+        gam0 = cpm / (cpm - 1.0 / Wbar0);
+      }
+    }
+    if constexpr (PSR) {  // inlet mass fractions into the slice, inlet enthalpy
+      const double Tin = io.Tin[i];
+      const double yi = isp ? io.Yin[(size_t)i * KK + s] : 0.0;
+      if (isp) Yin[s] = yi;
+      const double hk = isp ? nasa7_img(V, s, Tin, log(Tin), 1.0 / Tin).hRT * RU * Tin * rw : 0.0;
+      hin = wave_sum(yi * hk);
+    }
+    const double t = io.t[i];
+    if (lane == 0) {
+      R.cfg = cfg;
+      R.pfr = PF ? (prob == 3 ? 1 : (prob == 4 ? 2 : 0)) : 0;
+      R.conp = (prob == 1 || prob == 3);
+      R.energy = cfg->energy;
+      R.npv = cfg->prof_kind == 0 ? cfg->nprof : 0;
+      R.ntp = (cfg->prof_kind == 1 && cfg->energy == 2) ? cfg->nprof : 0;
+      R.rho0 = P0 * Wbar0 / (RU * T0);
+      R.V0 = (!R.conp && R.npv > 0) ? cfg->prof_v[0] : io.V0[i];
+      R.P0 = (R.conp && R.npv > 0) ? cfg->prof_v[0] : P0;
+      R.G = R.Pm = 0.0;
+      if constexpr (PF) {
+        if (R.pfr == 2) {
+          double dv;
+          engine_volume(cfg->eng, 0.0, R.V0, dv);
+          R.G = gam0;
+          R.Pm = T0;
+        }
+      }
+      R.mass = R.rho0 * R.V0;
+      if (PF && R.pfr == 1) {
+        R.G = R.rho0 * R.V0;
+        R.Pm = R.P0 + R.G * R.V0;
+      }
+      if constexpr (PSR) {
+        const bool vgiven = io.mode == 2;
+        const double mdot = io.mdot[i];
+        R.conp = 1;
+        R.pfr = vgiven ? 4 : 3;
+        R.Pm = hin;
+        R.G = vgiven ? mdot / R.V0 : 1.0 / R.V0;
+        R.mass = vgiven ? R.rho0 * R.V0 : R.V0 * mdot;
+      }
+      R.gfac = cfg->gfac;
+      R.qloss = cfg->qloss;
+      R.htc = cfg->htc;
+      R.areaq = cfg->areaq;
+      R.tamb = cfg->tamb;
+      R.nq = cfg->prof2_kind == 1 ? cfg->nprof2 : 0;
+      R.na = cfg->prof2_kind == 2 ? cfg->nprof2 : cfg->nprof3;
+      R.a_t = cfg->prof2_kind == 2 ? cfg->prof2_t : cfg->prof3_t;
+      R.a_v = cfg->prof2_kind == 2 ? cfg->prof2_v : cfg->prof3_v;
+      const int ar = io.afac_rxn ? io.afac_rxn[i] : -1;
+      R.pslot = (ar >= 0 && ar < img.II) ? img.slot_of[ar] : -1;
+      R.plnf = R.pslot >= 0 ? log(io.afac[i]) : 0.0;
+      R.tsel = t;  // the profile piece that contains the evaluation point
+    }
+    wave_lds_sync();
+    const double yl = lane <= KK ? io.y[(size_t)i * nv + lane] : 0.0;
+#ifdef CKMI_PHASE_TIMERS
+    unsigned long long sub[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const double fl = reactor_rhs<PL, PF, PSR>(V, R, t, yl, L, oJ, ncol, with_j, Yin, sub);
+#else
+    const double fl = reactor_rhs<PL, PF, PSR>(V, R, t, yl, L, oJ, ncol, with_j, Yin);
+#endif
+    if (lane <= KK) io.f[(size_t)i * nv + lane] = fl;
+    if (with_j) {
+      wave_lds_sync();
+      const double* Jsh = lds_at<const double>(oJ);
+      double* Jo = io.J + (size_t)i * nv * nv;
+      if (lane <= KK)  // lane = column: coalesced rows out, conflict-free column reads (LDJ is odd)
+        for (int r = 0; r < nv; ++r) Jo[(size_t)r * nv + lane] = Jsh[lane * LDJ + r];
+    }
+    wave_lds_sync();  // R, the slice and the J scratch are rewritten for the next state
+  }
+}
+
+template <bool PL, bool PF, bool PSR>
+int launch_rhs_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, int sel, int ncol,
+                     hipStream_t stream) {
+  const size_t lds = (size_t)m->img.bytes + align16(8 * ncol * LDJ) + slice_vec_bytes(m->G) +
+                     align16((int)sizeof(RunCtx)) + (PSR ? 8 * VL : 0);
+  int lds_max = 0;
+  CKMI_RK_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
+  if (lds > (size_t)lds_max)
+    return ckmi::set_error(CKMI_ERR_SIZE, "mechanism image + probe work space exceed the LDS of a CU");
+  const void* fn = (const void*)rhs_probe_kernel<PL, PF, PSR>;
+  if (lds > 64 * 1024) CKMI_RK_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const size_t cbytes = (sizeof(DevCfg) + 255) & ~(size_t)255;
+  void* ws = nullptr;
+  CKMI_RK_HIP_CHECK(hipMallocAsync(&ws, cbytes, stream));
+  int rc = stage_cfg(dc, (DevCfg*)ws, stream);
+  if (rc == CKMI_OK) {
+    hipLaunchKernelGGL((rhs_probe_kernel<PL, PF, PSR>), dim3(std::min(n, PROBE_GRID_MAX)), dim3(WAVE), lds, stream,
+                       m->img, (const DevCfg*)ws, n, sel, ncol, io);
+    CKMI_RK_HIP_CHECK(hipGetLastError());
+  }
+  CKMI_RK_HIP_CHECK(hipFreeAsync(ws, stream));
+  return rc;
+}
+
 }  // namespace

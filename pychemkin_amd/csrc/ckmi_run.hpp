@@ -101,6 +101,20 @@ struct PsrIO : ReactorIO {
   double ss_rtol, ss_atol;
 };
 
+// RHS / Jacobian probe (ckmi_reactor_rhs_jac, diagnostic): the initial state that fixes a reactor's context
+// (T0, P0, V0, Y0 as ReactorIO; V0 = tau_or_vol for an open reactor), the evaluation point (t, y [n][KK + 1])
+// and the outputs f [n][KK + 1], J [n][KK + 1][KK + 1] row-major (null: the plain pass, f only).
+struct ProbeIO {
+  const int* problem;
+  const double *T0, *P0, *V0, *Y0, *t, *y;
+  const int* afac_rxn;
+  const double* afac;
+  const double *Tin, *Yin, *mdot;  // open reactor (problem 5) only
+  int mode;                        // 1 residence time given, 2 volume given
+  double *f, *J;
+};
+constexpr int PROBE_GRID_MAX = 64;  // workgroups of a probe launch (states beyond it: grid-stride loop)
+
 // Integrator control state of one wave (wave-uniform scalars, kept in the wave's LDS slice).
 struct Ctl {
   int r, first, nflag, convfail, call_setup, failed, mm, ncf, nef, rc, isave, icrit, ncrit, status, nst, stopped;
