@@ -487,6 +487,36 @@ int ckmi_transport_fits(const ckmi_transport* tr, double* fits);
 int ckmi_species_viscosity(const ckmi_transport* tr, int32_t n, const double* T, double* visc, void* stream);
 int ckmi_mixture_viscosity(const ckmi_transport* tr, int32_t n, const double* T, const double* Y, double* visc,
                            void* stream);
+/* Diffusion coefficients: replaces KINGetDiffusionCoeffs (chemkin_wrapper.py:419-425, chemistry.py:1410-1470,
+ * mixture.py:1910), KINGetMixtureDiffusionCoeffs (:456-462, mixture.py:2015) and KINGetOrdinaryDiffusionCoeffs
+ * (:464-470, mixture.py:2066).  All results in cm^2/s; P in dyn/cm^2.
+ *   ckmi_diffusion_fit             host only: params [KK][6] as for ckmi_transport_fit -> dfits [KK][KK][4], the
+ *                                  coefficients of ln D_jk at 1 atm as a cubic in ln T (Chapman-Enskog with
+ *                                  Omega11* by Neufeld + 0.19 delta*^2 / T*, TRANLIB's combination rules with the
+ *                                  polar-nonpolar induction correction), same grid and least squares as
+ *                                  ckmi_transport_fit; symmetric in j and k
+ *   ckmi_transport_set_diffusion   uploads that table beside the viscosity tables; without it the three
+ *                                  functions below return CKMI_ERR_ARG
+ *   ckmi_binary_diffusion          T [n], P [n] -> D [n][KK][KK], D_jk = exp(cubic) 1 atm / P   (device pointers)
+ *   ckmi_mixture_diffusion         T [n], P [n], Y [KK][n] mass fractions -> D [KK][n], mixture-averaged
+ *                                  D_km = sum_{j != k} X_j W_j / (Wbar sum_{j != k} X_j / D_jk) with
+ *                                  X = (X+ + 1e-12) / sum (X+ + 1e-12), X+ from max(Y, 0)
+ *   ckmi_multicomponent_diffusion  same inputs -> D [n][KK][KK], the ordinary multicomponent coefficients
+ *                                  (Dixon-Lewis first order, TRANLIB MCMDIF: D_ij = X_i 16 T / (25 P) Wbar / W_j
+ *                                  (p_ij - p_ii), p = L^-1 by partial pivoting, D_ii = 0); info [n] is 0, or
+ *                                  k + 1 when the k-th pivot is exactly zero (dgetrf convention).  One wave per
+ *                                  state for KK <= 64, ckmi_lu_factor_batched per state up to KK = CKMI_LU_NMAX
+ *                                  (that path allocates a workspace of at most 256 MB and synchronises the stream
+ *                                  before it returns), CKMI_ERR_UNSUPPORTED above.
+ * An empty batch (n = 0) is a no-op. */
+int ckmi_diffusion_fit(int32_t KK, const double* wt, const double* params, double tlow, double thigh, double* dfits);
+int ckmi_transport_set_diffusion(ckmi_transport* tr, const double* dfits);
+int ckmi_binary_diffusion(const ckmi_transport* tr, int32_t n, const double* T, const double* P, double* D,
+                          void* stream);
+int ckmi_mixture_diffusion(const ckmi_transport* tr, int32_t n, const double* T, const double* P, const double* Y,
+                           double* D, void* stream);
+int ckmi_multicomponent_diffusion(const ckmi_transport* tr, int32_t n, const double* T, const double* P,
+                                  const double* Y, double* D, int32_t* info, void* stream);
 
 #ifdef __cplusplus
 }

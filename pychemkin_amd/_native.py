@@ -151,6 +151,11 @@ PROTOTYPES = {
     "ckmi_transport_set_conductivity": (ct.c_int, [_P, _P]),
     "ckmi_species_conductivity": (ct.c_int, [_P, ct.c_int32, _P, _P, _P]),
     "ckmi_mixture_conductivity": (ct.c_int, [_P, ct.c_int32, _P, _P, _P, _P]),
+    "ckmi_diffusion_fit": (ct.c_int, [ct.c_int32, _P, _P, ct.c_double, ct.c_double, _P]),
+    "ckmi_transport_set_diffusion": (ct.c_int, [_P, _P]),
+    "ckmi_binary_diffusion": (ct.c_int, [_P, ct.c_int32, _P, _P, _P, _P]),
+    "ckmi_mixture_diffusion": (ct.c_int, [_P, ct.c_int32, _P, _P, _P, _P, _P]),
+    "ckmi_multicomponent_diffusion": (ct.c_int, [_P, ct.c_int32, _P, _P, _P, _P, _P, _P]),
 }
 LU_NMAX = 192
 
@@ -679,11 +684,26 @@ def conductivity_fit(wt: np.ndarray, params: np.ndarray, thermo: np.ndarray, tlo
     return fits
 
 
-class DeviceTransport:
-    """Viscosity (and optionally conductivity) fits and Wilke tables of one DeviceMechanism, on its GPU
-    (wraps ckmi_transport)."""
+def diffusion_fit(wt: np.ndarray, params: np.ndarray, tlow: float, thigh: float) -> np.ndarray:
+    """Binary diffusion fits [KK][KK][4] (ln D_jk [cm2/s] at 1 atm as a cubic in ln T) from TRANLIB
+    parameters [KK][6]; host only."""
+    wt = np.ascontiguousarray(wt, dtype=np.float64)
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    KK = wt.shape[0]
+    if params.shape != (KK, 6):
+        raise NativeError(f"transport parameters must be [{KK}][6], got {params.shape}")
+    fits = np.zeros((KK, KK, 4))
+    _check(lib().ckmi_diffusion_fit(KK, wt.ctypes.data, params.ctypes.data, float(tlow), float(thigh),
+                                    fits.ctypes.data), "ckmi_diffusion_fit")
+    return fits
 
-    def __init__(self, dm: "DeviceMechanism", fits: np.ndarray, cond_fits: Optional[np.ndarray] = None):
+
+class DeviceTransport:
+    """Viscosity (and optionally conductivity and binary diffusion) fits and Wilke tables of one
+    DeviceMechanism, on its GPU (wraps ckmi_transport)."""
+
+    def __init__(self, dm: "DeviceMechanism", fits: np.ndarray, cond_fits: Optional[np.ndarray] = None,
+                 diff_fits: Optional[np.ndarray] = None):
         self.dm = dm
         self.KK = dm.KK
         fits = np.ascontiguousarray(fits, dtype=np.float64)
@@ -701,6 +721,14 @@ class DeviceTransport:
             with torch.cuda.device(dm.device):
                 _check(lib().ckmi_transport_set_conductivity(self._h, cf.ctypes.data), "ckmi_transport_set_conductivity")
             self.has_conductivity = True
+        self.has_diffusion = False
+        if diff_fits is not None:
+            df = np.ascontiguousarray(diff_fits, dtype=np.float64)
+            if df.shape != (self.KK, self.KK, 4):
+                raise NativeError(f"diffusion fits must be [{self.KK}][{self.KK}][4], got {df.shape}")
+            with torch.cuda.device(dm.device):
+                _check(lib().ckmi_transport_set_diffusion(self._h, df.ctypes.data), "ckmi_transport_set_diffusion")
+            self.has_diffusion = True
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -758,6 +786,50 @@ class DeviceTransport:
         with torch.cuda.device(self.dm.device):
             _check(lib().ckmi_mixture_conductivity(self._h, n, _ptr(T), _ptr(Y), _ptr(out),
                                                    _stream_ptr(self.dm.device)), "ckmi_mixture_conductivity")
+        return out
+
+    def binary_diffusion(self, T, P) -> torch.Tensor:
+        """T[n], P[n] [dyn/cm2] -> binary diffusion coefficients D[n][KK][KK] [cm2/s] (device tensor;
+        KINGetDiffusionCoeffs x n)."""
+        T = self.dm._dev(T).reshape(-1)
+        n = T.numel()
+        P = self.dm._dev(P).reshape(n)
+        out = torch.empty((n, self.KK, self.KK), dtype=torch.float64, device=self.dm.device)
+        with torch.cuda.device(self.dm.device):
+            _check(lib().ckmi_binary_diffusion(self._h, n, _ptr(T), _ptr(P), _ptr(out), _stream_ptr(self.dm.device)),
+                   "ckmi_binary_diffusion")
+        return out
+
+    def mixture_diffusion(self, T, P, Y_soa) -> torch.Tensor:
+        """T[n], P[n] [dyn/cm2], Y[KK][n] mass fractions -> mixture-averaged D[KK][n] [cm2/s] (device tensor)."""
+        T = self.dm._dev(T).reshape(-1)
+        n = T.numel()
+        P = self.dm._dev(P).reshape(n)
+        Y = self.dm._dev(Y_soa).reshape(self.KK, n)
+        out = torch.empty((self.KK, n), dtype=torch.float64, device=self.dm.device)
+        with torch.cuda.device(self.dm.device):
+            _check(lib().ckmi_mixture_diffusion(self._h, n, _ptr(T), _ptr(P), _ptr(Y), _ptr(out),
+                                                _stream_ptr(self.dm.device)), "ckmi_mixture_diffusion")
+        return out
+
+    def multicomponent_diffusion(self, T, P, Y_soa) -> torch.Tensor:
+        """T[n], P[n] [dyn/cm2], Y[KK][n] mass fractions -> ordinary multicomponent D[n][KK][KK] [cm2/s]
+        (device tensor; D[s, i, j] = D_ij, D_ii = 0).  Raises NativeError when a state's L matrix has an
+        exactly zero pivot."""
+        T = self.dm._dev(T).reshape(-1)
+        n = T.numel()
+        P = self.dm._dev(P).reshape(n)
+        Y = self.dm._dev(Y_soa).reshape(self.KK, n)
+        out = torch.empty((n, self.KK, self.KK), dtype=torch.float64, device=self.dm.device)
+        info = torch.zeros(n, dtype=torch.int32, device=self.dm.device)
+        with torch.cuda.device(self.dm.device):
+            _check(lib().ckmi_multicomponent_diffusion(self._h, n, _ptr(T), _ptr(P), _ptr(Y), _ptr(out), _ptr(info),
+                                                       _stream_ptr(self.dm.device)), "ckmi_multicomponent_diffusion")
+        bad = torch.nonzero(info)
+        if bad.numel():
+            s = int(bad[0, 0].item())
+            raise NativeError(f"ckmi_multicomponent_diffusion: zero pivot {int(info[s].item())} in state {s} "
+                              f"({bad.shape[0]} of {n} states singular)")
         return out
 
 

@@ -17,6 +17,8 @@ PARSE_SRC = os.path.join(HERE, "csrc", "ckmi_parse.cpp")  # native Chemkin-II in
 TRAN_SRC = os.path.join(HERE, "csrc", "ckmi_transport.hip")  # viscosity fits + species / mixture viscosity
 PSR_SRC = os.path.join(HERE, "csrc", "ckmi_psr.hip")  # steady-state PSRs: the open-reactor kernel instantiations
 EQUIL_SRC = os.path.join(HERE, "csrc", "ckmi_equil.hip")  # batched chemical equilibrium and CJ states
+DIFF_SRC = os.path.join(HERE, "csrc", "ckmi_diffusion.hip")  # binary / mixture-averaged / multicomponent diffusion
+TRAN_HDR = os.path.join(HERE, "csrc", "ckmi_transport.hpp")  # the ckmi_transport tables both transport units share
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("ckmi_device.hpp", "ckmi_reactor.hpp", "ckmi_image.hpp",
                                                 "ckmi_run.hpp", "ckmi_internal.hpp", "ckmi_reactor_kernel.hpp")] + [
     os.path.join(HERE, "..", "include", "ckmi.h"), os.path.join(HERE, "..", "include", "ckmi_kin.h")]
@@ -41,6 +43,9 @@ BIG_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-mcode-object
              # the blocked Gauss-Jordan's MFMA accumulators are the register-resident matrix itself:
              # VGPR-form MFMA (1249 -> 24 spilled VGPRs at NB = 11)
              "-mllvm", "-amdgpu-mfma-vgpr-form"]
+# the wave-per-state Gauss-Jordan of the multicomponent kernel is a fully unrolled KK x NC loop nest (the row
+# must stay in VGPRs)
+DIFF_FLAGS = LU_FLAGS + ["-mllvm", "-pragma-unroll-threshold=2000000"]
 KIN_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", f"--offload-arch={ARCH}"]  # host code only
 
 
@@ -52,7 +57,7 @@ def _stale(target: str, sources) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(OUT, [SRC, LU_SRC, BIG_SRC, KIN_SRC, JIT_SRC, PARSE_SRC, TRAN_SRC, PSR_SRC, EQUIL_SRC] + DEPS)
+    return _stale(OUT, [SRC, LU_SRC, BIG_SRC, KIN_SRC, JIT_SRC, PARSE_SRC, TRAN_SRC, PSR_SRC, EQUIL_SRC, DIFF_SRC, TRAN_HDR] + DEPS)
 
 
 PROF_OUT = os.path.join(HERE, "_lib", "libckmi_prof.so")  # diagnostic phase-timer build
@@ -69,7 +74,8 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
     """Build libckmi.so (or the phase-timer build, or an A/B variant at `out` with `extra` flags).
 
     Separately compiled translation units (the reactor kernel alone takes ~2 min) linked into one
-    shared library: ckmi.hip, ckmi_psr.hip, ckmi_equil.hip, ckmi_lu.hip, ckmi_big.hip and the host-only ckmi_kin.cpp,
+    shared library: ckmi.hip, ckmi_psr.hip, ckmi_equil.hip, ckmi_lu.hip, ckmi_big.hip, ckmi_transport.hip,
+    ckmi_diffusion.hip and the host-only ckmi_kin.cpp,
     ckmi_parse.cpp and ckmi_jit.cpp (linked with libhiprtc)."""
     default = out is None and not prof and not extra
     out = out or (PROF_OUT if prof else OUT)
@@ -96,8 +102,11 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
     if force or _stale(parse_obj, [PARSE_SRC] + DEPS):
         jobs.append((PARSE_SRC, parse_obj, KIN_FLAGS))
     tran_obj = os.path.join(OBJ_DIR, "ckmi_transport.o")
-    if force or _stale(tran_obj, [TRAN_SRC] + DEPS):
+    if force or _stale(tran_obj, [TRAN_SRC, TRAN_HDR] + DEPS):
         jobs.append((TRAN_SRC, tran_obj, LU_FLAGS))
+    diff_obj = os.path.join(OBJ_DIR, "ckmi_diffusion.o")
+    if force or _stale(diff_obj, [DIFF_SRC, TRAN_HDR] + DEPS):
+        jobs.append((DIFF_SRC, diff_obj, DIFF_FLAGS))
     # the open-reactor (PSR) kernels: a translation unit of their own, same flags as the reactor kernel
     psr_obj = os.path.join(OBJ_DIR, "ckmi_psr.o")
     if force or _stale(psr_obj, [PSR_SRC] + DEPS):
@@ -118,7 +127,7 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
         for f in [pool.submit(_compile, s, o, fl, verbose) for s, o, fl in jobs]:
             f.result()
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, main_obj, lu_obj, big_obj, kin_obj, jit_obj,
-           parse_obj, tran_obj, psr_obj, equil_obj,
+           parse_obj, tran_obj, diff_obj, psr_obj, equil_obj,
            "-L/opt/rocm/lib", "-lhiprtc", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)

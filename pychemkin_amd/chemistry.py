@@ -145,6 +145,30 @@ class Chemistry:
             self._cfits_version = self._version
         return self._cfits.copy()
 
+    @property
+    def diffusion_fits(self) -> np.ndarray:
+        """[KK][KK][4] coefficients of ln D_jk [cm2/s] at 1 atm in powers of ln T (ckmi_diffusion_fit)."""
+        if self._tran_params is None:
+            raise ChemistryError("no transport data processed")
+        if getattr(self, "_dfits", None) is None or self._dfits_version != self._version:
+            self._dfits = _transport.diffusion_fits(self._mech.wt, self._tran_params)
+            self._dfits_version = self._version
+        return self._dfits.copy()
+
+    def SpeciesDiffusionCoeffs(self, press: float = 0.0, temp: float = 0.0) -> np.ndarray:
+        """Binary diffusion coefficients [KK, KK] [cm2/s] at press [dyn/cm2] and temp [K], on the GPU
+        (chemistry.py:1410-1470, KINGetDiffusionCoeffs -> ckmi_binary_diffusion)."""
+        import torch
+
+        if temp <= 0.0:
+            raise ChemistryError("temperature must be > 0")
+        if press <= 0.0:
+            raise ChemistryError("pressure must be > 0")
+        dt = self.device_transport()
+        T = torch.tensor([float(temp)], dtype=torch.float64, device=dt.dm.device)
+        P = torch.tensor([float(press)], dtype=torch.float64, device=dt.dm.device)
+        return dt.binary_diffusion(T, P)[0].cpu().numpy()
+
     def SpeciesCond(self, temp: float = 0.0) -> np.ndarray:
         """Species thermal conductivities [erg/(cm s K)] at temp, on the GPU (chemistry.py:1361-1396,
         KINGetConductivity -> ckmi_species_conductivity)."""

@@ -1211,6 +1211,9 @@ int KINPreProcess(int* isurf, int* itran, char* chem, char* surf, char* therm, c
     if (!rc) rc = ckmi_conductivity_fit(KK, s->wt.data(), params.data(), s->thermo.data(), CKMI_VISC_FIT_TLOW,
                                         CKMI_VISC_FIT_THIGH, cfits.data());
     if (!rc) rc = ckmi_transport_set_conductivity(s->tran, cfits.data());
+    std::vector<double> dfits((size_t)4 * KK * KK);
+    if (!rc) rc = ckmi_diffusion_fit(KK, s->wt.data(), params.data(), CKMI_VISC_FIT_TLOW, CKMI_VISC_FIT_THIGH, dfits.data());
+    if (!rc) rc = ckmi_transport_set_diffusion(s->tran, dfits.data());
     if (!rc) {
       for (int k = 0; k < KK; ++k) {
         std::copy(fits.begin() + 4 * k, fits.begin() + 4 * k + 4, f8.begin() + 8 * k);
@@ -1316,6 +1319,85 @@ int KINGetMixtureConductivity(int* chemset, double* T, double* Y, double* cond) 
   rc = ckmi_mixture_conductivity(s->tran, 1, s->dbuf, s->dbuf + 1, s->dbuf + 1 + KK, nullptr);
   if (rc) return fail(rc, ckmi_last_error());
   return hip_ok(hipMemcpy(cond, s->dbuf + 1 + KK, sizeof(double), hipMemcpyDeviceToHost), "D2H");
+}
+
+namespace {
+// One state through a diffusion kernel: scratch layout T, P, Y [KK] (mass fractions, when given), then `nout`
+// doubles of output and one slot for the multicomponent kernel's info.  kind 0 binary, 1 mixture-averaged,
+// 2 multicomponent; out receives the device result as it lies there.
+int diffusion_state(int* chemset, const double* P, const double* T, const double* Y, int kind, std::vector<double>& out) {
+  ChemSet* s = get_set(chemset);
+  if (!s || !P || !T || (kind != 0 && !Y) || !(*T > 0.0) || !(*P > 0.0)) return fail(CKMI_ERR_ARG, "bad argument");
+  if (!s->tran) return fail(CKMI_ERR_ARG, "no transport data processed (KINPreProcess with itran = 1)");
+  const int KK = s->KK;
+  const size_t nout = kind == 1 ? (size_t)KK : (size_t)KK * KK;
+  int rc = ensure_scratch(s, 3 + (size_t)KK + nout);
+  if (rc) return rc;
+  (void)hipSetDevice(s->device);
+  std::vector<double> in(2 + KK, 0.0);
+  in[0] = *T;
+  in[1] = *P;
+  if (Y) std::copy(Y, Y + KK, in.begin() + 2);
+  if ((rc = hip_ok(hipMemcpy(s->dbuf, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice), "H2D"))) return rc;
+  double* dT = s->dbuf;
+  double* dP = s->dbuf + 1;
+  double* dY = s->dbuf + 2;
+  double* dD = s->dbuf + 2 + KK;
+  int32_t* dinfo = reinterpret_cast<int32_t*>(dD + nout);
+  rc = kind == 0   ? ckmi_binary_diffusion(s->tran, 1, dT, dP, dD, nullptr)
+       : kind == 1 ? ckmi_mixture_diffusion(s->tran, 1, dT, dP, dY, dD, nullptr)
+                   : ckmi_multicomponent_diffusion(s->tran, 1, dT, dP, dY, dD, dinfo, nullptr);
+  if (rc) return fail(rc, ckmi_last_error());
+  out.resize(nout);
+  if ((rc = hip_ok(hipMemcpy(out.data(), dD, nout * sizeof(double), hipMemcpyDeviceToHost), "D2H"))) return rc;
+  if (kind == 2) {
+    int32_t info = 0;
+    if ((rc = hip_ok(hipMemcpy(&info, dinfo, sizeof(info), hipMemcpyDeviceToHost), "D2H"))) return rc;
+    if (info != 0) return fail(CKMI_ERR_ARG, "singular multicomponent L matrix (zero pivot " + std::to_string(info) + ")");
+  }
+  return CKMI_OK;
+}
+// device row-major [KK][KK] -> the caller's F-order array: element (j, k) at j + KK k
+void to_fortran(const std::vector<double>& d, int KK, double* out) {
+  for (int j = 0; j < KK; ++j)
+    for (int k = 0; k < KK; ++k) out[j + (size_t)KK * k] = d[(size_t)j * KK + k];
+}
+}  // namespace
+
+// KINGetDiffusionCoeffs (chemkin_wrapper.py:419-425, chemistry.py:1410-1470, mixture.py:1910): binary
+// diffusion coefficients [cm2/s] at P [dyn/cm2] and T into an F-order [KK, KK] array
+int KINGetDiffusionCoeffs(int* chemset, double* P, double* T, double* D) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (!D) return fail(CKMI_ERR_ARG, "bad argument");
+  std::vector<double> d;
+  const int rc = diffusion_state(chemset, P, T, nullptr, 0, d);
+  if (rc) return rc;
+  to_fortran(d, get_set(chemset)->KK, D);
+  return CKMI_OK;
+}
+
+// KINGetMixtureDiffusionCoeffs (chemkin_wrapper.py:456-462, mixture.py:2015): mixture-averaged diffusion
+// coefficients [cm2/s]; the composition is read as MASS fractions, as mixture.py:2051 passes self.Y
+int KINGetMixtureDiffusionCoeffs(int* chemset, double* P, double* T, double* Y, double* D) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (!D) return fail(CKMI_ERR_ARG, "bad argument");
+  std::vector<double> d;
+  const int rc = diffusion_state(chemset, P, T, Y, 1, d);
+  if (rc) return rc;
+  std::copy(d.begin(), d.end(), D);
+  return CKMI_OK;
+}
+
+// KINGetOrdinaryDiffusionCoeffs (chemkin_wrapper.py:464-470, mixture.py:2066): ordinary multicomponent
+// diffusion coefficients [cm2/s] into an F-order [KK, KK] array, mass fractions as above
+int KINGetOrdinaryDiffusionCoeffs(int* chemset, double* P, double* T, double* Y, double* D) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (!D) return fail(CKMI_ERR_ARG, "bad argument");
+  std::vector<double> d;
+  const int rc = diffusion_state(chemset, P, T, Y, 2, d);
+  if (rc) return rc;
+  to_fortran(d, get_set(chemset)->KK, D);
+  return CKMI_OK;
 }
 
 // KINGetGasReactionString (chemkin_wrapper.py:365-371, chemistry.py:1759-1781): 1-based reaction index
@@ -1636,10 +1718,8 @@ int KINCalculateEqGasWithOption(int* chemset, int* option, int* realgas, double*
 // PFR, engines, flames) and return CKMI_ERR_UNSUPPORTED with a message.
 #define CKMI_OUT_OF_SCOPE(name, what, ...) \
   int name(__VA_ARGS__) { return fail(CKMI_ERR_UNSUPPORTED, #name ": " what " is not on this path"); }
-CKMI_OUT_OF_SCOPE(KINGetDiffusionCoeffs, "transport", int*, double*, double*, double*)
-CKMI_OUT_OF_SCOPE(KINGetMixtureDiffusionCoeffs, "transport", int*, double*, double*, double*, double*)
-CKMI_OUT_OF_SCOPE(KINGetOrdinaryDiffusionCoeffs, "transport", int*, double*, double*, double*, double*)
-CKMI_OUT_OF_SCOPE(KINGetThermalDiffusionCoeffs, "transport", int*, double*, double*, double*, double*, double*)
+CKMI_OUT_OF_SCOPE(KINGetThermalDiffusionCoeffs, "thermal diffusion (the full multicomponent L matrix)", int*, double*,
+                  double*, double*, double*, double*)
 CKMI_OUT_OF_SCOPE(KINAll0D_SetupPSRReactorInputs, "the PSR model", int*, int*, double*, double*, double*, double*,
                   double*, double*, double*, double*, double*, double*)
 CKMI_OUT_OF_SCOPE(KINAll0D_SetupPSRInletInputs, "the PSR model", int*, int*, int*, double*, double*, double*)

@@ -23,6 +23,8 @@
 // Bound: FP64 VALU (KK^2 x 6 FLOP per state); HBM traffic is (KK + 2) x 8 B per state.
 // Conductivity (KINGetConductivity / KINGetMixtureConductivity, mixture.py:1885-1909,1979-2013):
 // lambda_k from the ln-T cubic of ckmi_conductivity_fit, mixed by lambda = (sum X lambda + 1 / sum X / lambda) / 2.
+// Diffusion: the binary fits (ckmi_diffusion_fit) and their upload (ckmi_transport_set_diffusion) are here, beside
+// the other host fits; the kernels that evaluate them are in ckmi_diffusion.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -33,18 +35,7 @@
 
 #include "../../include/ckmi.h"
 #include "ckmi_internal.hpp"
-
-struct ckmi_transport {
-  int device = 0;
-  int KK = 0;
-  double* fits = nullptr;  // device [KK][4]
-  double* A = nullptr;     // device [KK][KK]
-  double* B = nullptr;     // device [KK][KK]
-  double* cfits = nullptr; // device [KK][4] conductivity fits (ckmi_transport_set_conductivity), else NULL
-  const double* wt = nullptr;  // the mechanism's device weights
-  std::vector<double> fits_host;
-  std::vector<double> cfits_host;
-};
+#include "ckmi_transport.hpp"
 
 namespace {
 
@@ -60,6 +51,13 @@ int fail(int code, const std::string& msg) { return ckmi::set_error(code, msg); 
 double omega22(double tstar, double dstar) {
   return 1.16145 * std::pow(tstar, -0.14874) + 0.52487 * std::exp(-0.77320 * tstar) +
          2.16178 * std::exp(-2.43787 * tstar) + 0.2 * dstar * dstar / tstar;
+}
+
+// Omega11* (Neufeld-Janzen-Aziz) with the polar term 0.19 delta*^2 / T*: the self-diffusion coefficient of the
+// conductivity fit and the binary diffusion coefficients of ckmi_diffusion_fit
+double omega11(double ts, double dstar) {
+  return 1.06036 * std::pow(ts, -0.15610) + 0.19300 * std::exp(-0.47635 * ts) +
+         1.03587 * std::exp(-1.52996 * ts) + 1.76474 * std::exp(-3.89411 * ts) + 0.19 * dstar * dstar / ts;
 }
 
 // least squares min |V c - y| for the FIT_NPTS x FIT_ORDER Vandermonde matrix V by Householder QR
@@ -228,8 +226,7 @@ int ckmi_conductivity_fit(int32_t KK, const double* wt, const double* params, co
       if (geo == 0) {
         lam = 3.75 * R * eta / wt[k];
       } else {
-        const double om11 = 1.06036 * std::pow(ts, -0.15610) + 0.19300 * std::exp(-0.47635 * ts) +
-                            1.03587 * std::exp(-1.52996 * ts) + 1.76474 * std::exp(-3.89411 * ts) + 0.19 * dstar * dstar / ts;
+        const double om11 = omega11(ts, dstar);
         const double kT = KB * T;
         const double rhoD = 3.0 / 16.0 * std::sqrt(2.0 * M_PI * kT * kT * kT / (0.5 * m)) / (M_PI * sig * sig * om11) * m / kT;
         const double x = rhoD / eta;
@@ -249,6 +246,58 @@ int ckmi_conductivity_fit(int32_t KK, const double* wt, const double* params, co
     }
     lsq_qr(V, y, fits + FIT_ORDER * k);
   }
+  return CKMI_OK;
+}
+
+int ckmi_diffusion_fit(int32_t KK, const double* wt, const double* params, double tlow, double thigh, double* dfits) {
+  // D_jk = 3/16 sqrt(2 pi (kB T)^3 / m_jk) / (P pi sigma_jk^2 Omega11*(T / eps_jk, delta*_jk)) at P = 1 atm
+  // (Chapman-Enskog, TRANFIT), m_jk the reduced mass; eps_jk, sigma_jk, mu_jk by TRANLIB's combination rules:
+  // geometric / arithmetic / geometric for two polar or two nonpolar species, and for a polar p with a
+  // nonpolar n the induction correction xi = 1 + alpha*_n mu*_p^2 sqrt(eps_p / eps_n) / 4 (eps_jk scaled by
+  // xi^2, sigma_jk by xi^-1/6, mu_jk = 0); then ln D_jk as a cubic in ln T on the grid of ckmi_transport_fit
+  if (KK <= 0 || !wt || !params || !dfits) return fail(CKMI_ERR_ARG, "ckmi_diffusion_fit: bad argument");
+  if (!(tlow > 0.0) || !(thigh > tlow)) return fail(CKMI_ERR_ARG, "ckmi_diffusion_fit: need 0 < tlow < thigh");
+  for (int k = 0; k < KK; ++k) {
+    const double* p = params + 6 * k;
+    if (!(p[1] > 0.0) || !(p[2] > 0.0) || !(wt[k] > 0.0) || !(p[3] >= 0.0) || !(p[4] >= 0.0))
+      return fail(CKMI_ERR_ARG, "ckmi_diffusion_fit: species " + std::to_string(k) +
+                                    " needs eps/k > 0, sigma > 0, W > 0, dipole >= 0, polarizability >= 0");
+  }
+  for (int j = 0; j < KK; ++j)
+    for (int k = j; k < KK; ++k) {
+      const double* pj = params + 6 * j;
+      const double* pk = params + 6 * k;
+      const double epsj = pj[1], sigj = pj[2] * ANGSTROM, muj = pj[3] * DEBYE;
+      const double epsk = pk[1], sigk = pk[2] * ANGSTROM, muk = pk[3] * DEBYE;
+      double eps = std::sqrt(epsj * epsk), sig = 0.5 * (sigj + sigk), mu2 = muj * muk;
+      if ((muj > 0.0) != (muk > 0.0)) {
+        const bool jpolar = muj > 0.0;
+        const double epsp = jpolar ? epsj : epsk, sigp = jpolar ? sigj : sigk, mup = jpolar ? muj : muk;
+        const double epsn = jpolar ? epsk : epsj, sign = jpolar ? sigk : sigj;
+        const double alphan = (jpolar ? pk[4] : pj[4]) * ANGSTROM * ANGSTROM * ANGSTROM;
+        const double xi = 1.0 + 0.25 * (alphan / (sign * sign * sign)) * (mup * mup / (epsp * KB * sigp * sigp * sigp)) *
+                                    std::sqrt(epsp / epsn);
+        eps *= xi * xi;
+        sig *= std::pow(xi, -1.0 / 6.0);
+        mu2 = 0.0;
+      }
+      const double dstar = 0.5 * mu2 / (eps * KB * sig * sig * sig);
+      const double mjk = wt[j] * wt[k] / (wt[j] + wt[k]) / NA;
+      double V[FIT_NPTS][FIT_ORDER], y[FIT_NPTS];
+      for (int i = 0; i < FIT_NPTS; ++i) {
+        const double T = tlow + (thigh - tlow) * i / (FIT_NPTS - 1);
+        const double kT = KB * T;
+        const double D = 3.0 / 16.0 * std::sqrt(2.0 * M_PI * kT * kT * kT / mjk) /
+                         (ckmi_tran::P_ATM * M_PI * sig * sig * omega11(T / eps, dstar));
+        const double x = std::log(T);
+        V[i][0] = 1.0;
+        for (int c = 1; c < FIT_ORDER; ++c) V[i][c] = V[i][c - 1] * x;
+        y[i] = std::log(D);
+      }
+      double* c = dfits + FIT_ORDER * ((size_t)j * KK + k);
+      lsq_qr(V, y, c);
+      std::copy(c, c + FIT_ORDER, dfits + FIT_ORDER * ((size_t)k * KK + j));
+    }
   return CKMI_OK;
 }
 
@@ -305,6 +354,21 @@ int ckmi_transport_set_conductivity(ckmi_transport* t, const double* cfits) {
   return rc;
 }
 
+int ckmi_transport_set_diffusion(ckmi_transport* t, const double* dfits) {
+  if (!t || !dfits) return fail(CKMI_ERR_ARG, "ckmi_transport_set_diffusion: null argument");
+  const size_t bytes = sizeof(double) * FIT_ORDER * (size_t)t->KK * t->KK;
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  if (prev != t->device) (void)hipSetDevice(t->device);
+  int rc = CKMI_OK;
+  if (!t->dfits && hipMalloc(&t->dfits, bytes) != hipSuccess)
+    rc = fail(CKMI_ERR_HIP, "ckmi_transport_set_diffusion: device allocation failed");
+  else if (hipMemcpy(t->dfits, dfits, bytes, hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(CKMI_ERR_HIP, "ckmi_transport_set_diffusion: upload failed");
+  if (prev >= 0 && prev != t->device) (void)hipSetDevice(prev);
+  return rc;
+}
+
 int ckmi_species_conductivity(const ckmi_transport* t, int32_t n, const double* T, double* cond, void* stream) {
   if (!t || n < 0 || !T || !cond) return fail(CKMI_ERR_ARG, "ckmi_species_conductivity: bad argument");
   if (!t->cfits) return fail(CKMI_ERR_ARG, "ckmi_species_conductivity: no conductivity fits (ckmi_transport_set_conductivity)");
@@ -331,6 +395,7 @@ int ckmi_mixture_conductivity(const ckmi_transport* t, int32_t n, const double* 
 
 int ckmi_transport_destroy(ckmi_transport* t) {
   if (!t) return CKMI_OK;
+  (void)hipFree(t->dfits);
   (void)hipFree(t->cfits);
   (void)hipFree(t->fits);
   (void)hipFree(t->A);

@@ -52,7 +52,8 @@ def device_transport(chem, device_index: int = None):
     dt = _tcache.get(key)
     if dt is None or dt.version != chem._version:
         cf = chem.conductivity_fits if chem._tran_params is not None else None
-        dt = _native.DeviceTransport(dm, chem._vfits, cf)
+        df = chem.diffusion_fits if chem._tran_params is not None else None
+        dt = _native.DeviceTransport(dm, chem._vfits, cf, df)
         dt.version = chem._version
         _tcache[key] = dt
     return dt

@@ -447,6 +447,51 @@ class Mixture:
         Y = torch.as_tensor(self.Y.reshape(self._KK, 1).copy(), dtype=torch.float64, device=dt.dm.device)
         return float(dt.mixture_conductivity(T, Y)[0].item())
 
+    def _need_transport_TP(self, composition: bool):
+        self._need_transport()
+        if not self._Pset:
+            raise MixtureError("mixture pressure [dynes/cm2] is not provided")
+        if composition and not (self._Xset or self._Yset):
+            raise MixtureError("mixture composition is not provided")
+
+    def _diffusion_state(self, dt):
+        import torch
+
+        T = torch.tensor([self._temp], dtype=torch.float64, device=dt.dm.device)
+        P = torch.tensor([self._press], dtype=torch.float64, device=dt.dm.device)
+        return T, P
+
+    def species_Diffusion_Coeffs(self) -> np.ndarray:
+        """Binary diffusion coefficients [KK, KK] [cm2/s] at the mixture temperature and pressure, on the GPU
+        (KINGetDiffusionCoeffs, mixture.py:1910)."""
+        self._need_transport_TP(False)
+        dt = self._chem.device_transport()
+        T, P = self._diffusion_state(dt)
+        return dt.binary_diffusion(T, P)[0].cpu().numpy()
+
+    def mixture_diffusion_coeffs(self) -> np.ndarray:
+        """Mixture-averaged diffusion coefficients [KK] [cm2/s] (KINGetMixtureDiffusionCoeffs with the mass
+        fractions, mixture.py:2015): D_km = sum_{j != k} X_j W_j / (Wbar sum_{j != k} X_j / D_jk) on the GPU."""
+        import torch
+
+        self._need_transport_TP(True)
+        dt = self._chem.device_transport()
+        T, P = self._diffusion_state(dt)
+        Y = torch.as_tensor(self.Y.reshape(self._KK, 1).copy(), dtype=torch.float64, device=dt.dm.device)
+        return dt.mixture_diffusion(T, P, Y)[:, 0].cpu().numpy()
+
+    def mixture_binary_diffusion_coeffs(self) -> np.ndarray:
+        """Ordinary multicomponent diffusion coefficients [KK, KK] [cm2/s], element [i, j] = D_ij
+        (KINGetOrdinaryDiffusionCoeffs with the mass fractions, mixture.py:2066; the reference names them
+        "binary"), Dixon-Lewis first order on the GPU."""
+        import torch
+
+        self._need_transport_TP(True)
+        dt = self._chem.device_transport()
+        T, P = self._diffusion_state(dt)
+        Y = torch.as_tensor(self.Y.reshape(self._KK, 1).copy(), dtype=torch.float64, device=dt.dm.device)
+        return dt.multicomponent_diffusion(T, P, Y)[0].cpu().numpy()
+
     def massROP(self) -> np.ndarray:
         """Species mass rates of production [g/cm3-s]."""
         return self.ROP() * self._WT

@@ -77,3 +77,11 @@ def conductivity_fits(wt: np.ndarray, params: np.ndarray, thermo: np.ndarray) ->
     from . import _native
 
     return _native.conductivity_fit(wt, params, thermo, FIT_TLOW, FIT_THIGH)
+
+
+def diffusion_fits(wt: np.ndarray, params: np.ndarray) -> np.ndarray:
+    """[KK][KK][4] ln-T cubic fits of the binary diffusion coefficients ln D_jk [cm2/s] at 1 atm (host C++:
+    ckmi_diffusion_fit; Chapman-Enskog with TRANLIB's combination rules, symmetric in j and k)."""
+    from . import _native
+
+    return _native.diffusion_fit(wt, params, FIT_TLOW, FIT_THIGH)
