@@ -341,6 +341,54 @@ int ckmi_psr_run(const ckmi_mech* mech, const ckmi_reactor_cfg* cfg, const ckmi_
                  const double* tau_or_vol, const double* Tguess, const double* Yguess, double* Tss, double* Yss,
                  double* rho, double* tau_res, double* vol, double* resid, int32_t* stats, void* stream);
 
+/* Batched networks of steady-state PSRs with recycle streams (the reference's hybridreactornetwork.ReactorNetwork,
+ * one network and one reactor at a time there).  n_net independent networks of R reactors each, solved by
+ * Gauss-Seidel sweeps in the order given: for position i = 0..R-1 the effective inlet of reactor i
+ * is mixed by mass and enthalpy from its external inlets and from the upstream solutions present (a mixing kernel,
+ * one wave per network), ckmi_psr_run solves that position of every active network in one launch, and a tear kernel
+ * ends the sweep.  Through-flows come once from the linear balance (I - F^T) mdot = mdot_ext.  A feed-forward
+ * network (no split entry j -> i with j >= i) takes exactly one sweep; the others sweep until the change of every
+ * tear-point reactor between two sweeps satisfies |dT| <= tear_rtol T and |dY_k| <= tear_atol + tear_rtol |Y_k|
+ * (all of them, not any of them as the reference tests), or max_sweeps is reached.  A network that declares no
+ * tear point but has recycle is tested at every reactor.  Networks that are done leave the active list (rebuilt in
+ * network order after every sweep) and are not integrated again; a network's result does not depend on the rest of
+ * the batch.  R <= CKMI_NET_RMAX and KK + 1 <= 64 (CKMI_ERR_UNSUPPORTED above); E >= 1.
+ * cfg[R], psr[R] and guess_mode[R] are HOST arrays, one entry per position; everything else is a device pointer:
+ *   P [n_net][R] dyn/cm2; tau_or_vol [n_net][R] s or cm3 by psr[i].mode
+ *   split [n_net][R][R+1]      mass fraction of reactor j's outflow that enters reactor i; column R leaves the network
+ *   ext_mdot, ext_T [n_net][R][E], ext_Y [n_net][R][E][KK]   external inlets in E padded slots (mdot = 0: unused)
+ *   Tguess [n_net][R], Yguess [n_net][R][KK]; guess_mode[i] 0: the estimate as given, 1: Tguess with the effective
+ *                              inlet's composition (reset_estimate_composition(inlet.X)); later sweeps start from the
+ *                              reactor's previous solution
+ *   tear [n_net][R] int32      1: a tear point
+ *   Tss, mdot, rho, tau_res, vol, resid [n_net][R], Yss [n_net][R][KK], stats [n_net][R][CKMI_NSTAT]   per reactor
+ *                              (mdot: the through-flow g/s)
+ *   net_stats [n_net][CKMI_NET_NSTAT] int32, tear_resid [n_net]   per network: status, sweeps taken, flags, and the
+ *                              last scaled tear residual (<= 1: converged; 0 for a feed-forward network)
+ * The call synchronises the stream once per sweep (a 4-byte count of active networks sizes the next launches). */
+typedef struct {
+  int32_t max_sweeps;          /* 0 = 200 */
+  double tear_rtol, tear_atol; /* 0 = 1e-6, 1e-8 */
+  double relax;                /* new = old + relax (new - old) after every sweep but the first; 0 = 1 */
+} ckmi_network_cfg;
+#define CKMI_NET_RMAX 16
+#define CKMI_NET_STAT_STATUS 0
+#define CKMI_NET_STAT_SWEEPS 1
+#define CKMI_NET_STAT_FLAGS 2 /* bit 0: feed-forward, bit 1: no tear point declared, every reactor is tested */
+#define CKMI_NET_NSTAT 4
+#define CKMI_NET_OK 0
+#define CKMI_NET_TEAR_LIMIT 10      /* max_sweeps reached (the reference's code) */
+#define CKMI_NET_REACTOR_FAILED 11  /* a member's stats say which reactor and why; the network stops there */
+#define CKMI_NET_FLOW_SINGULAR 12   /* the flow balance has no solution (a closed loop with no exit) or leaves a
+                                       reactor without through-flow; the network is never integrated (outputs NaN) */
+int ckmi_psr_network_run(const ckmi_mech* mech, int32_t n_net, int32_t R, int32_t E, const ckmi_reactor_cfg* cfg,
+                         const ckmi_psr_cfg* psr, const ckmi_network_cfg* net, const int32_t* guess_mode,
+                         const double* P, const double* split, const double* ext_mdot, const double* ext_T,
+                         const double* ext_Y, const double* tau_or_vol, const double* Tguess, const double* Yguess,
+                         const int32_t* tear, double* Tss, double* Yss, double* mdot, double* rho, double* tau_res,
+                         double* vol, double* resid, int32_t* stats, int32_t* net_stats, double* tear_resid,
+                         void* stream);
+
 /* Batched gas-phase chemical equilibrium and Chapman-Jouguet detonation states (ideal gas, element
  * potentials; replaces KINCalculateEquil / KINCalculateEquilWithOption / KINCalculateEqGasWithOption,
  * chemkin_wrapper.py:513-541, mixture.py:3574-3961, one state per call there).  n independent states per

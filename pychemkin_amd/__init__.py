@@ -6,8 +6,8 @@ and the plug-flow reactors (``pychemkin_amd.flowreactors.PFR``, on the same kern
 batched entry point BatchSweep.  Numerics run in hand-written gfx950 HIP kernels
 (libckmi.so, include/ckmi.h).  Units are cgs as the reference sets with KINSetUnitSystem(1).
 """
-from .batch import (BatchEquilibrium, BatchPSR, BatchResult, BatchSweep, EquilibriumResult, PSRResult,
-                    afactor_sensitivity)
+from .batch import (BatchEquilibrium, BatchPSR, BatchPSRNetwork, BatchResult, BatchSweep, EquilibriumResult,
+                    NetworkResult, PSRResult, afactor_sensitivity)
 from .batchreactor import (
     BatchReactors,
     GivenPressureBatchReactor_EnergyConservation,

@@ -89,6 +89,17 @@ class RhsPsr(ct.Structure):
 RUN_NOT_STEADY = 6  # CKMI_RUN_NOT_STEADY: a PSR reached t_max before the steady-state rule was met
 
 
+class NetworkCfg(ct.Structure):
+    """ckmi_network_cfg: a zero field selects its default (200 sweeps, tear tolerances 1e-6 / 1e-8, relax 1)."""
+    _fields_ = [("max_sweeps", ct.c_int32), ("tear_rtol", ct.c_double), ("tear_atol", ct.c_double),
+                ("relax", ct.c_double)]
+
+
+NET_RMAX = 16   # CKMI_NET_RMAX
+NET_NSTAT = 4   # CKMI_NET_NSTAT: status, sweeps, flags (1 feed-forward, 2 every reactor is a tear point), reserved
+NET_OK, NET_TEAR_LIMIT, NET_REACTOR_FAILED, NET_FLOW_SINGULAR = 0, 10, 11, 12
+
+
 class EquilCfg(ct.Structure):
     """ckmi_equil_cfg: a zero field selects its default (tol 1e-12, max_iter 200, V / V1 in [0.30, 0.97] from
     0.60, cj_tol 1e-9, cj_iter 40)."""
@@ -121,6 +132,8 @@ PROTOTYPES = {
     "ckmi_engine_heat_rates": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.c_double, ct.c_double, _P, ct.c_int32, _P, _P,
                                           _P, _P, _P]),
     "ckmi_psr_run": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.POINTER(PsrCfg), ct.c_int32] + [_P] * 15),
+    "ckmi_psr_network_run": (ct.c_int, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(ReactorCfg),
+                                         ct.POINTER(PsrCfg), ct.POINTER(NetworkCfg), ct.POINTER(ct.c_int32)] + [_P] * 20),
     "ckmi_reactor_rhs_jac": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.c_int32] + [_P] * 7 +
                              [ct.POINTER(ReactorExt), ct.POINTER(RhsPsr), _P, _P, _P]),
     "ckmi_equil_run": (ct.c_int, [_P, ct.POINTER(EquilCfg), ct.c_int32] + [_P] * 11),
@@ -562,6 +575,52 @@ class DeviceMechanism:
         # the inputs stay referenced by the result (the launch is asynchronous on this stream)
         return dict(T=Tss, Y=Yss, rho=rho, tau=tau, vol=vol, resid=resid, stats=stats,
                     _inputs=[P, Tin, Yin, mdot, tv, Tg, Yg])
+
+    def psr_network_run(self, cfgs, modes, ss_tols, guess_mode, P, split, ext_mdot, ext_T, ext_Y, tau_or_vol, Tguess,
+                        Yguess, tear, max_sweeps: int = 0, tear_rtol: float = 0.0, tear_atol: float = 0.0,
+                        relax: float = 0.0):
+        """n_net networks of R steady-state PSRs with recycle streams (ckmi_psr_network_run, include/ckmi.h).
+
+        cfgs [R] ReactorCfg, modes [R] (1 residence time, 2 volume), ss_tols [R] (ss_rtol, ss_atol) and
+        guess_mode [R] are per position; P, tau_or_vol, Tguess [n_net][R]; split [n_net][R][R+1]; ext_mdot,
+        ext_T [n_net][R][E]; ext_Y [n_net][R][E][KK]; Yguess [n_net][R][KK]; tear [n_net][R] int32.
+        Returns a dict of device tensors: T, Y, mdot, rho, tau, vol, resid, stats per reactor and net_stats,
+        tear_resid per network.  Synchronises the stream once per sweep."""
+        split = self._dev(split)
+        if split.dim() != 3 or split.shape[2] != split.shape[1] + 1:
+            raise ValueError("split must be [n_net][R][R+1]")
+        n, R = int(split.shape[0]), int(split.shape[1])
+        ext_mdot = self._dev(ext_mdot)
+        if ext_mdot.dim() != 3 or tuple(ext_mdot.shape[:2]) != (n, R) or ext_mdot.shape[2] < 1:
+            raise ValueError("ext_mdot must be [n_net][R][E] with E >= 1")
+        E = int(ext_mdot.shape[2])
+        ext_T = self._dev(ext_T).reshape(n, R, E)
+        ext_Y = self._dev(ext_Y).reshape(n, R, E, self.KK)
+        P, tv, Tg = (self._dev(v).reshape(n, R) for v in (P, tau_or_vol, Tguess))
+        Yg = self._dev(Yguess).reshape(n, R, self.KK)
+        tear = self._dev(tear, torch.int32).reshape(n, R)
+        if not (len(cfgs) == len(modes) == len(ss_tols) == len(guess_mode) == R):
+            raise ValueError("cfgs, modes, ss_tols and guess_mode need one entry per position")
+        cfg_arr = (ReactorCfg * R)()
+        for i, c in enumerate(cfgs):
+            ct.memmove(ct.byref(cfg_arr, i * ct.sizeof(ReactorCfg)), ct.byref(c), ct.sizeof(ReactorCfg))
+        psr_arr = (PsrCfg * R)(*[PsrCfg(int(m), float(t[0]), float(t[1])) for m, t in zip(modes, ss_tols)])
+        gm = (ct.c_int32 * R)(*[int(g) for g in guess_mode])
+        nc = NetworkCfg(int(max_sweeps), float(tear_rtol), float(tear_atol), float(relax))
+        f64 = dict(dtype=torch.float64, device=self.device)
+        Tss, mdot, rho, tau, vol, resid = (torch.empty((n, R), **f64) for _ in range(6))
+        Yss = torch.empty((n, R, self.KK), **f64)
+        stats = torch.empty((n, R, NSTAT), dtype=torch.int32, device=self.device)
+        net_stats = torch.empty((n, NET_NSTAT), dtype=torch.int32, device=self.device)
+        tear_resid = torch.empty(n, **f64)
+        with torch.cuda.device(self.device):
+            _check(lib().ckmi_psr_network_run(self._h, n, R, E, cfg_arr, psr_arr, ct.byref(nc), gm, _ptr(P), _ptr(split),
+                                              _ptr(ext_mdot), _ptr(ext_T), _ptr(ext_Y), _ptr(tv), _ptr(Tg), _ptr(Yg),
+                                              _ptr(tear), _ptr(Tss), _ptr(Yss), _ptr(mdot), _ptr(rho), _ptr(tau),
+                                              _ptr(vol), _ptr(resid), _ptr(stats), _ptr(net_stats), _ptr(tear_resid),
+                                              _stream_ptr(self.device)), "ckmi_psr_network_run")
+        return dict(T=Tss, Y=Yss, mdot=mdot, rho=rho, tau=tau, vol=vol, resid=resid, stats=stats, net_stats=net_stats,
+                    tear_resid=tear_resid, _inputs=[P, split, ext_mdot, ext_T, ext_Y, tv, Tg, Yg, tear, cfgs])
 
     def equil_run(self, option, T, P, Y, tol: float = 0.0, max_iter: int = 0, cj_bracket=(0.0, 0.0),
                   cj_start: float = 0.0, cj_tol: float = 0.0, cj_iter: int = 0):

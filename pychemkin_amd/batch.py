@@ -290,6 +290,230 @@ class BatchPSR:
 
 
 @dataclass
+class NetworkResult:
+    T: np.ndarray            # [n, R] steady-state temperatures [K]
+    Y: np.ndarray            # [n, R, KK] mass fractions
+    mdot: np.ndarray         # [n, R] through-flow of every reactor [g/s] (the linear flow balance)
+    rho: np.ndarray          # [n, R] density [g/cm3]
+    tau: np.ndarray          # [n, R] residence time [s]
+    volume: np.ndarray       # [n, R] volume [cm3]
+    resid: np.ndarray        # [n, R] scaled residual of the steady-state rule at the last solve (<= 1: steady)
+    stats: np.ndarray        # [n, R, 8] int32 solver statistics of the last solve (see _native.STAT_NAMES)
+    P: np.ndarray            # [n, R] pressure [dyn/cm2]
+    split: np.ndarray        # [n, R, R + 1] the outflow split the networks were run with (column R: the exit)
+    status: np.ndarray       # [n] 0 ok, 10 tear iteration limit, 11 a reactor failed, 12 flow balance singular
+    sweeps: np.ndarray       # [n] Gauss-Seidel sweeps taken
+    tear_resid: np.ndarray   # [n] scaled change of the tear points over the last sweep (<= 1: converged)
+    feed_forward: np.ndarray  # [n] bool: no recycle, solved in one sweep
+    wt: np.ndarray
+
+    @property
+    def X(self) -> np.ndarray:
+        x = self.Y / self.wt
+        return x / x.sum(axis=-1, keepdims=True)
+
+    @property
+    def reactor_status(self) -> np.ndarray:
+        """[n, R] status of every reactor's last solve (0 steady, -1 no inlet stream reached it)."""
+        return self.stats[:, :, 6]
+
+    @property
+    def exit_mdot(self) -> np.ndarray:
+        """[n, R] mass flow rate that leaves the network from every reactor [g/s] (0: no exit there)."""
+        return self.mdot * self.split[:, :, -1]
+
+    def exit_streams(self, net: int = 0):
+        """The exit streams of network `net`: a list of (reactor index, mdot [g/s], T [K], Y) for every reactor
+        with an exit fraction."""
+        return [(i, float(self.exit_mdot[net, i]), float(self.T[net, i]), self.Y[net, i].copy())
+                for i in range(self.T.shape[1]) if self.split[net, i, -1] > 0.0]
+
+
+class BatchPSRNetwork:
+    """Many independent networks of R steady-state PSRs with recycle streams, one ckmi_psr_network_run call per
+    GPU (the reference's hybridreactornetwork.ReactorNetwork solves one network, one reactor at a
+    time).  Gauss-Seidel over the reactors in the order given, tear-stream iteration when there is recycle.
+
+    Every per-position option (mode, energy, the tolerances, heat loss) is a scalar or a sequence of R values."""
+
+    ESTIMATES = ("given", "inlet", "burnt")
+
+    def __init__(self, chem: Chemistry, R: int, mode="residence_time", energy="ENERGY", ss_rtol=1.0e-8, ss_atol=1.0e-14,
+                 rtol=1.0e-8, atol=1.0e-14, t_max=0.0, qloss=0.0, htc=0.0, areaq=0.0, tamb=300.0, gfac=1.0,
+                 max_steps: int = 0, max_sweeps: int = 200, tear_rtol: float = 1.0e-6, tear_atol: float = 1.0e-8,
+                 relax: float = 1.0, devices: Optional[Sequence[int]] = None):
+        R = int(R)
+        if R < 1 or R > _native.NET_RMAX:
+            raise ValueError(f"a network has 1..{_native.NET_RMAX} reactors")
+
+        def per(v, what):
+            seq = [v] * R if isinstance(v, (str, int, float, np.floating, np.integer)) else list(v)
+            if len(seq) != R:
+                raise ValueError(f"{what} needs one value or {R} values")
+            return seq
+
+        self.chem, self.R = chem, R
+        modes = per(mode, "mode")
+        if any(m not in ("residence_time", "volume") for m in modes):
+            raise ValueError('mode must be "residence_time" or "volume"')
+        self.modes = [1 if m == "residence_time" else 2 for m in modes]
+        en = [ENERGIES[e] for e in per(energy, "energy")]
+        self.ss_tols = list(zip(map(float, per(ss_rtol, "ss_rtol")), map(float, per(ss_atol, "ss_atol"))))
+        self.max_sweeps, self.tear_rtol, self.tear_atol, self.relax = int(max_sweeps), float(tear_rtol), \
+            float(tear_atol), float(relax)
+        if self.max_sweeps < 1 or self.tear_rtol <= 0.0 or self.tear_atol < 0.0 or self.relax <= 0.0:
+            raise ValueError("max_sweeps must be >= 1, tear_rtol > 0, tear_atol >= 0 and relax > 0")
+        if any(self.tear_rtol < t[0] for t in self.ss_tols):
+            raise ValueError("tear_rtol must be >= ss_rtol of every position: the tear test cannot resolve changes "
+                             "below the steady-state rule of the reactors")
+        opts = [per(v, k) for k, v in (("rtol", rtol), ("atol", atol), ("t_max", t_max), ("qloss", qloss), ("htc", htc),
+                                       ("areaq", areaq), ("tamb", tamb), ("gfac", gfac))]
+        self.cfgs = [_native.make_cfg(energy=en[i], t_end=opts[2][i], atol=max(opts[1][i], 1e-20),
+                                      rtol=max(opts[0][i], 1e-12), qloss=opts[3][i], htc=opts[4][i], areaq=opts[5][i],
+                                      tamb=opts[6][i], gfac=opts[7][i], max_steps=max_steps) for i in range(R)]
+        self.devices = list(devices) if devices is not None else None
+
+    _devices = BatchSweep._devices
+
+    @staticmethod
+    def check_split(split: np.ndarray) -> None:
+        """ValueError unless every split row sums to 1 within 1e-12, every fraction lies in [0, 1] and no reactor
+        feeds itself.  split [..., R, R + 1]."""
+        if np.any(~np.isfinite(split)) or np.any(split < 0.0) or np.any(split > 1.0):
+            raise ValueError("split fractions must lie in [0, 1]")
+        if np.any(np.abs(split.sum(axis=-1) - 1.0) > 1e-12):
+            raise ValueError("every split row must sum to 1 (within 1e-12): a reactor's outflow goes somewhere")
+        R = split.shape[-2]
+        if np.any(split[..., np.arange(R), np.arange(R)] != 0.0):
+            raise ValueError("a reactor cannot feed itself")
+
+    def run(self, P, split, ext_mdot, ext_T, ext_X=None, ext_Y=None, tau=None, volume=None, estimate="burnt",
+            T_estimate=None, X_estimate=None, Y_estimate=None, tear=None) -> NetworkResult:
+        """Solve networks 0..n-1; every input broadcasts over the networks (give it without the leading axis).
+
+        P [n, R] dyn/cm2; split [n, R, R + 1] (row j: where reactor j's outflow goes, last column the exit);
+        ext_mdot, ext_T [n, R, E] and ext_X or ext_Y [n, R, E, KK]: the external inlets in E padded slots
+        (mdot = 0: unused); tau / volume [n, R] by each position's mode; tear [n, R] marks the tear points.
+        estimate: one of "given" (T_estimate and X_estimate / Y_estimate), "inlet" (T_estimate with the effective
+        inlet's composition) and "burnt" (BatchPSR.burnt_estimate on the network's combined external feed at the
+        reactor's pressure; T_estimate overrides its temperature), or one per reactor."""
+        import torch
+
+        R, KK = self.R, self.chem.KK
+        wt = self.chem.WT
+        split = np.asarray(split, dtype=np.float64)
+        ext_mdot = np.asarray(ext_mdot, dtype=np.float64)
+        ext_T = np.asarray(ext_T, dtype=np.float64)
+        if split.shape[-2:] != (R, R + 1):
+            raise ValueError(f"split must be [..., {R}, {R + 1}]")
+        if ext_mdot.ndim < 2 or ext_mdot.shape[-2] != R:
+            raise ValueError(f"ext_mdot must be [..., {R}, E]")
+        E = ext_mdot.shape[-1]
+        ext_f = ext_Y if ext_Y is not None else ext_X
+        if ext_f is None:
+            raise ValueError("ext_X or ext_Y is required")
+        ext_f = np.asarray(ext_f, dtype=np.float64)
+        if ext_f.shape[-3:] != (R, E, KK):
+            raise ValueError(f"the external inlets' fractions must be [..., {R}, {E}, {KK}]")
+        tv_in = [None if v is None else np.asarray(v, dtype=np.float64) for v in (tau, volume)]
+        n = 1
+        for a, nd in ((split, 3), (ext_mdot, 3), (ext_T, 3), (ext_f, 4), (np.asarray(P), 2), (tv_in[0], 2),
+                      (tv_in[1], 2), (None if T_estimate is None else np.asarray(T_estimate), 2),
+                      (None if tear is None else np.asarray(tear), 2)):
+            if a is not None and a.ndim == nd:
+                n = max(n, a.shape[0])
+        split = np.ascontiguousarray(np.broadcast_to(split, (n, R, R + 1)))
+        ext_mdot = np.ascontiguousarray(np.broadcast_to(ext_mdot, (n, R, E)))
+        ext_T = np.ascontiguousarray(np.broadcast_to(ext_T, (n, R, E)))
+        ext_f = np.broadcast_to(ext_f, (n, R, E, KK))
+        if ext_Y is None:
+            yy = ext_f * wt
+            s = yy.sum(axis=-1, keepdims=True)
+            ext_f = np.where(s > 0.0, yy / np.where(s > 0.0, s, 1.0), 0.0)
+        ext_Yv = np.ascontiguousarray(ext_f)
+        P = np.ascontiguousarray(np.broadcast_to(np.asarray(P, dtype=np.float64), (n, R)))
+        tv = np.empty((n, R))
+        for i, m in enumerate(self.modes):
+            v = tv_in[m - 1]
+            if v is None:
+                raise ValueError(f"reactor {i}: " + ("tau is required" if m == 1 else "volume is required"))
+            tv[:, i] = np.broadcast_to(v, (n, R))[:, i]
+        tear = np.zeros((n, R), np.int32) if tear is None else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(tear).astype(np.int32), (n, R)))
+        # ---- validation
+        self.check_split(split)
+        if np.any(ext_mdot < 0.0) or np.any(~np.isfinite(ext_mdot)):
+            raise ValueError("external mass flow rates must be >= 0")
+        if np.any(ext_mdot[:, 0].sum(axis=-1) <= 0.0):
+            raise ValueError("the first reactor of a network needs an external inlet")
+        used = ext_mdot > 0.0
+        if np.any(P <= 0.0) or np.any(tv <= 0.0) or np.any(ext_T[used] <= 0.0):
+            raise ValueError("P, tau / volume and the inlet temperatures must be > 0")
+        if np.any(np.abs(ext_Yv[used].sum(axis=-1) - 1.0) > 1e-9):
+            raise ValueError("the fractions of a used external inlet must sum to 1")
+        # ---- estimates
+        est = [estimate] * R if isinstance(estimate, str) else list(estimate)
+        if len(est) != R or any(e not in self.ESTIMATES for e in est):
+            raise ValueError(f'estimate must be one of {self.ESTIMATES}, or {R} of them')
+        Tg = np.full((n, R), np.nan) if T_estimate is None else \
+            np.broadcast_to(np.asarray(T_estimate, dtype=np.float64), (n, R)).copy()
+        Yg = np.zeros((n, R, KK))
+        Yg[:, :, 0] = 1.0
+        if any(e == "given" for e in est):
+            f = Y_estimate if Y_estimate is not None else X_estimate
+            if f is None:
+                raise ValueError('estimate="given" needs X_estimate or Y_estimate')
+            f = np.broadcast_to(np.asarray(f, dtype=np.float64), (n, R, KK))
+            if Y_estimate is None:
+                f = f * wt
+                f = f / f.sum(axis=-1, keepdims=True)
+            for i in range(R):
+                if est[i] == "given":
+                    Yg[:, i] = f[:, i]
+        if any(e == "burnt" for e in est):
+            m_all = ext_mdot.reshape(n, R * E)
+            feed = np.einsum("ns,nsk->nk", m_all, ext_Yv.reshape(n, R * E, KK)) / m_all.sum(axis=1, keepdims=True)
+            cols = [i for i in range(R) if est[i] == "burnt"]
+            helper = BatchPSR(self.chem, devices=self.devices)
+            Tb, Yb = helper.burnt_estimate(P[:, cols].reshape(-1), np.repeat(feed, len(cols), axis=0))
+            Tb, Yb = Tb.reshape(n, len(cols)), Yb.reshape(n, len(cols), KK)
+            for c, i in enumerate(cols):
+                Yg[:, i] = Yb[:, c]
+                Tg[:, i] = np.where(np.isnan(Tg[:, i]), Tb[:, c], Tg[:, i])
+        if np.any(np.isnan(Tg)) or np.any(Tg <= 0.0):
+            raise ValueError('estimates "given" and "inlet" need T_estimate > 0')
+        gmode = [1 if e == "inlet" else 0 for e in est]
+        # ---- launches
+        devs = self._devices()
+        if not devs:
+            raise _native.NativeError("no ROCm GPU visible: BatchPSRNetwork requires at least one MI355X")
+        shards = [np.arange(r, n, len(devs)) for r in range(len(devs))]
+        pending = []
+        for d, idx in zip(devs, shards):
+            if idx.size == 0:
+                continue
+            dm = self.chem.device_mechanism(d)
+            with torch.cuda.device(d):
+                res = dm.psr_network_run(self.cfgs, self.modes, self.ss_tols, gmode, P[idx], split[idx], ext_mdot[idx],
+                                         ext_T[idx], ext_Yv[idx], tv[idx], Tg[idx], Yg[idx], tear[idx],
+                                         max_sweeps=self.max_sweeps, tear_rtol=self.tear_rtol, tear_atol=self.tear_atol,
+                                         relax=self.relax)
+            pending.append((idx, res))
+        out = NetworkResult(T=np.empty((n, R)), Y=np.empty((n, R, KK)), mdot=np.empty((n, R)), rho=np.empty((n, R)),
+                            tau=np.empty((n, R)), volume=np.empty((n, R)), resid=np.empty((n, R)),
+                            stats=np.empty((n, R, _native.NSTAT), np.int32), P=P, split=split,
+                            status=np.empty(n, np.int32), sweeps=np.empty(n, np.int32), tear_resid=np.empty(n),
+                            feed_forward=np.empty(n, bool), wt=wt)
+        for idx, res in pending:
+            for name, key in (("T", "T"), ("Y", "Y"), ("mdot", "mdot"), ("rho", "rho"), ("tau", "tau"),
+                              ("volume", "vol"), ("resid", "resid"), ("stats", "stats"), ("tear_resid", "tear_resid")):
+                getattr(out, name)[idx] = res[key].cpu().numpy()
+            ns = res["net_stats"].cpu().numpy()
+            out.status[idx], out.sweeps[idx], out.feed_forward[idx] = ns[:, 0], ns[:, 1], (ns[:, 2] & 1) != 0
+        return out
+
+
+@dataclass
 class EquilibriumResult:
     T: np.ndarray            # equilibrium temperature [K]
     P: np.ndarray            # equilibrium pressure [dyn/cm2]

@@ -18,6 +18,7 @@ TRAN_SRC = os.path.join(HERE, "csrc", "ckmi_transport.hip")  # viscosity fits + 
 PSR_SRC = os.path.join(HERE, "csrc", "ckmi_psr.hip")  # steady-state PSRs: the open-reactor kernel instantiations
 EQUIL_SRC = os.path.join(HERE, "csrc", "ckmi_equil.hip")  # batched chemical equilibrium and CJ states
 DIFF_SRC = os.path.join(HERE, "csrc", "ckmi_diffusion.hip")  # binary / mixture-averaged / multicomponent diffusion
+NET_SRC = os.path.join(HERE, "csrc", "ckmi_network.hip")  # PSR networks: flow balance, stream mixing, tear iteration
 TRAN_HDR = os.path.join(HERE, "csrc", "ckmi_transport.hpp")  # the ckmi_transport tables both transport units share
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("ckmi_device.hpp", "ckmi_reactor.hpp", "ckmi_image.hpp",
                                                 "ckmi_run.hpp", "ckmi_internal.hpp", "ckmi_reactor_kernel.hpp")] + [
@@ -57,7 +58,7 @@ def _stale(target: str, sources) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(OUT, [SRC, LU_SRC, BIG_SRC, KIN_SRC, JIT_SRC, PARSE_SRC, TRAN_SRC, PSR_SRC, EQUIL_SRC, DIFF_SRC, TRAN_HDR] + DEPS)
+    return _stale(OUT, [SRC, LU_SRC, BIG_SRC, KIN_SRC, JIT_SRC, PARSE_SRC, TRAN_SRC, PSR_SRC, EQUIL_SRC, DIFF_SRC, NET_SRC, TRAN_HDR] + DEPS)
 
 
 PROF_OUT = os.path.join(HERE, "_lib", "libckmi_prof.so")  # diagnostic phase-timer build
@@ -74,7 +75,7 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
     """Build libckmi.so (or the phase-timer build, or an A/B variant at `out` with `extra` flags).
 
     Separately compiled translation units (the reactor kernel alone takes ~2 min) linked into one
-    shared library: ckmi.hip, ckmi_psr.hip, ckmi_equil.hip, ckmi_lu.hip, ckmi_big.hip, ckmi_transport.hip,
+    shared library: ckmi.hip, ckmi_psr.hip, ckmi_network.hip, ckmi_equil.hip, ckmi_lu.hip, ckmi_big.hip, ckmi_transport.hip,
     ckmi_diffusion.hip and the host-only ckmi_kin.cpp,
     ckmi_parse.cpp and ckmi_jit.cpp (linked with libhiprtc)."""
     default = out is None and not prof and not extra
@@ -115,6 +116,10 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
     equil_obj = os.path.join(OBJ_DIR, "ckmi_equil.o")
     if force or _stale(equil_obj, [EQUIL_SRC] + DEPS):
         jobs.append((EQUIL_SRC, equil_obj, FLAGS))
+    # the PSR-network coupling kernels (small; the reactors themselves are ckmi_psr.hip's)
+    net_obj = os.path.join(OBJ_DIR, "ckmi_network.o")
+    if force or _stale(net_obj, [NET_SRC] + DEPS):
+        jobs.append((NET_SRC, net_obj, LU_FLAGS))
     # a variant that only names the workgroup kernel shares the default build's ckmi.hip object
     main_extra = [f for f in extra if "CKMI_BIG" not in f]
     # (a phase-timer build never shares the production object, and vice versa)
@@ -127,7 +132,7 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
         for f in [pool.submit(_compile, s, o, fl, verbose) for s, o, fl in jobs]:
             f.result()
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, main_obj, lu_obj, big_obj, kin_obj, jit_obj,
-           parse_obj, tran_obj, diff_obj, psr_obj, equil_obj,
+           parse_obj, tran_obj, diff_obj, psr_obj, equil_obj, net_obj,
            "-L/opt/rocm/lib", "-lhiprtc", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)

@@ -2,13 +2,17 @@
 
 Drop-in subset used by the plug-flow reactor (flowreactors/PFR.py): one of mass flow rate [g/s],
 volumetric flow rate [cm3/s], velocity [cm/s] (with a flow area) or SCCM, converted to the others
-at the stream's state as inlet.py:86-236 does (SCCM at 298.15 K and 1 atm).
+at the stream's state as inlet.py:86-236 does (SCCM at 298.15 K and 1 atm).  The stream utilities of the reactor
+networks (clone_stream, compare_streams, adiabatic_mixing_streams; inlet.py:508-682) follow the class.
 """
 from __future__ import annotations
 
+import copy
+from typing import Tuple
+
 from .chemistry import Chemistry
 from .constants import P_ATM, R_GAS
-from .mixture import Mixture, MixtureError
+from .mixture import Mixture, MixtureError, compare_mixtures
 
 
 class Stream(Mixture):
@@ -114,3 +118,45 @@ class Stream(Mixture):
             raise MixtureError("velocity must be > 0")
         self._flowratemode = 2
         self._inletflowrate[2] = float(vel)
+
+
+# ---------------------------------------------------------------------- stream utilities (inlet.py:508-682)
+def clone_stream(source: Stream, target: Stream):
+    """Copy temperature, pressure, mass flow rate and mole fractions of `source` onto `target`."""
+    if source.chemID != target.chemID:
+        raise MixtureError("the streams have different Chemistry Sets")
+    target.temperature = source.temperature
+    target.pressure = source.pressure
+    target.mass_flowrate = source.mass_flowrate
+    target.X = source.X
+
+
+def compare_streams(streamA: Stream, streamB: Stream, atol: float = 1.0e-10, rtol: float = 1.0e-3,
+                    mode: str = "mass") -> Tuple[bool, float, float]:
+    """compare_mixtures plus the mass flow rate.  Returns (issame, the largest absolute difference, the largest
+    relative difference).  As in the reference the flow-rate verdict is joined to the mixtures' by `or`."""
+    issame, diff_max, var_max = compare_mixtures(streamA, streamB, atol=atol, rtol=rtol, mode=mode)
+    mflr_diff = abs(streamA.mass_flowrate - streamB.mass_flowrate)
+    mflr_var = mflr_diff / streamA.mass_flowrate
+    flowsame = mflr_diff <= atol or mflr_var <= rtol
+    return bool(issame or flowsame), max(diff_max, mflr_diff), max(var_max, mflr_var)
+
+
+def adiabatic_mixing_streams(streamA: Stream, streamB: Stream) -> Stream:
+    """The stream of A and B mixed adiabatically: the mass flow rates add, the mass fractions mix by mass and the
+    temperature conserves the total enthalpy flux.  A copy of A (its pressure and label) carries the result.
+
+    The temperature comes from the mechanism's NASA-7 tables on the host, iterated to convergence (the reference
+    stops once a Newton correction is below 0.1 K); no GPU is needed."""
+    if not isinstance(streamA, Stream) or not isinstance(streamB, Stream):
+        raise MixtureError("the streams must be Stream objects")
+    if streamA.chemID != streamB.chemID:
+        raise MixtureError("the streams have different Chemistry Sets")
+    from .stirreactors.openreactor import mix_streams
+
+    T, Y, mdot = mix_streams(streamA.chemistry, [streamA, streamB])
+    final = copy.deepcopy(streamA)
+    final.mass_flowrate = mdot
+    final.Y = Y
+    final.temperature = T
+    return final

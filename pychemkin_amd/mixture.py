@@ -21,7 +21,7 @@ from typing import List, Tuple, Union
 import numpy as np
 
 from .chemistry import Chemistry
-from .constants import R_GAS
+from .constants import P_ATM, R_GAS
 from .utilities import calculate_stoichiometrics
 
 
@@ -572,6 +572,46 @@ def interpolate_mixtures(mixtureleft: Mixture, mixtureright: Mixture, ratio: flo
         m.volume = (1.0 - ratio) * mixtureleft.volume + ratio * mixtureright.volume
     m.Y = (1.0 - ratio) * mixtureleft.Y + ratio * mixtureright.Y
     return m
+
+
+def compare_mixtures(mixtureA: Mixture, mixtureB: Mixture, atol: float = 1.0e-10, rtol: float = 1.0e-3,
+                     mode: str = "mass") -> Tuple[bool, float, float]:
+    """Compare mixture B against mixture A (reference mixture.py:3386-3569): pressure (absolute difference in
+    atm), temperature and the species mass or mole fractions.  Returns (issame, the largest absolute
+    difference, the largest relative difference).
+
+    The verdict follows the reference: the pressure and temperature tests are joined by `or` (equal
+    pressures therefore pass whatever the temperatures), and any species whose difference exceeds both
+    tolerances makes it False.  A species with |fraction| <= atol in A has relative difference 0.  The
+    reference's "mole" branch collects the species that agree instead of those that differ; both modes
+    collect those that differ here.  The maxima cover pressure, temperature and the differing species."""
+    for m, which in ((mixtureA, "first"), (mixtureB, "second")):
+        if not isinstance(m, Mixture):
+            raise MixtureError(f"the {which} argument must be a Mixture object")
+        if m.validate() != 0:
+            raise MixtureError(f"the {which} mixture is not fully defined")
+    if mixtureA.chemID != mixtureB.chemID:
+        raise MixtureError("the Mixtures belong to different Chemistry Sets")
+    if mode.lower() not in ("mass", "mole"):
+        raise MixtureError('mode must be "mass" or "mole"')
+    pres_diff = abs(mixtureA.pressure - mixtureB.pressure)
+    pres_var = pres_diff / mixtureA.pressure
+    pres_diff /= P_ATM
+    issame = pres_diff <= atol or pres_var <= rtol
+    temp_diff = abs(mixtureA.temperature - mixtureB.temperature)
+    temp_var = temp_diff / mixtureA.temperature
+    issame = issame or temp_diff <= atol or temp_var <= rtol
+    diff_max, var_max = max(pres_diff, temp_diff), max(pres_var, temp_var)
+    fa, fb = (mixtureA.X, mixtureB.X) if mode.lower() == "mole" else (mixtureA.Y, mixtureB.Y)
+    spec_diff = np.abs(fa - fb)
+    tiny = np.abs(fa) <= atol
+    spec_var = np.where(tiny, 0.0, spec_diff / np.where(tiny, 1.0, fa))
+    ok = np.where(tiny, issame | (spec_diff <= atol), (spec_diff <= atol) | (spec_var <= rtol))
+    if not np.all(ok):
+        issame = False
+        diff_max = max(diff_max, float(spec_diff[~ok].max()))
+        var_max = max(var_max, float(spec_var[~ok].max()))
+    return bool(issame), float(diff_max), float(var_max)
 
 
 def _combine(recipe, mode: str):

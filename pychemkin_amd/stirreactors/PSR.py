@@ -15,7 +15,8 @@ burnt estimate stays ignited and an unburnt one may blow out to the inlet state 
 tau = 1 ms from an unburnt 1700 K estimate does); the reference's TWOPNT Newton search can land on either
 branch from the same estimate.  set_estimate_conditions("HP") sets a burnt estimate.
 
-Reactor networks, clusters and surface chemistry are not covered.
+Networks of these reactors are solved by ``pychemkin_amd.hybridreactornetwork.ReactorNetwork``; clusters and
+surface chemistry are not covered.
 """
 from __future__ import annotations
 
