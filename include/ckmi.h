@@ -455,8 +455,9 @@ int ckmi_engine_heat_rates(const ckmi_mech* mech, const ckmi_reactor_cfg* cfg, d
  *   J [n][KK+1][KK+1]                 row-major, J[i][j] = d f_i / d y_j; NULL: the plain pass, f only.  The wave
  *                                     kernel's J is FP64; the workgroup kernel's comes back through the FP32 slot it
  *                                     parks its Jacobian in.  Plug flow: scaled by rho / G like f.
- * The kernel and its template parameters are chosen as ckmi_reactor_run / ckmi_psr_run choose them from the
- * mechanism, the problems, cfg->rtol and ckmi_set_reactor_path.  CKMI_ERR_UNSUPPORTED: problem 4 or 5 with
+ * The kernel and its template parameters come from the chooser ckmi_reactor_run / ckmi_psr_run call (wave_plan /
+ * big_plan of csrc/ckmi_dispatch.hpp, readable through ckmi_reactor_variant), on the mechanism, the problems,
+ * cfg->rtol and ckmi_set_reactor_path.  CKMI_ERR_UNSUPPORTED: problem 4 or 5 with
  * KK + 1 > 64 (problem 4 also on the forced workgroup path); CKMI_ERR_SIZE: an image the workgroup kernel's LDS
  * does not hold; CKMI_ERR_ARG: a problem outside 1..5, n < 0, a missing array.  All arrays are device pointers;
  * the call synchronises the stream once (it reads problem[] on the host). */
@@ -483,6 +484,21 @@ int ckmi_set_reactor_path(int32_t path);
  * species and G third-body groups on a CU with lds_max bytes of LDS; -1 if none fits.  A mechanism
  * whose image is larger gets CKMI_ERR_SIZE from ckmi_reactor_run. */
 int ckmi_big_max_image_bytes(int32_t nvar, int32_t KKp, int32_t G, int32_t lds_max);
+
+/* Host-only query of the variant chooser (no GPU needed, no state read or written): the compiled variant
+ * ckmi_reactor_run (open_reactor = 0) or ckmi_psr_run (open_reactor = 1) and the probes of
+ * ckmi_reactor_rhs_jac launch for nvar = KK + 1 state variables, a mechanism with / without PLOG-class
+ * (has_plog) and FORD / RORD / fractional-order (has_general) reactions, cfg->rtol and the
+ * ckmi_set_reactor_path value path.
+ *   out[0]  1: the wave-per-reactor kernel, 2: the workgroup-per-reactor kernel
+ *   wave:      out[1] N of the FP32-inverse launch (0: none), out[2] N of the FP64-inverse launch, out[3] PL,
+ *              out[4] what the FP64-inverse launch takes: 0 every reactor, 1 plug flow and engines only,
+ *              2 those and the reactors the FP32-inverse launch failed on
+ *   workgroup: out[1] NB, out[3] PL, the rest 0
+ * CKMI_ERR_UNSUPPORTED as the run: nvar > 192, or an open reactor with nvar > 64; CKMI_ERR_ARG: nvar < 2, a path
+ * outside 0..3 or out = NULL. */
+int ckmi_reactor_variant(int32_t nvar, int32_t has_plog, int32_t has_general, double rtol, int32_t path,
+                         int32_t open_reactor, int32_t out[5]);
 
 /* Batched dense LU of Newton iteration matrices too large for one wave (mechanisms with more
  * than 63 species).  Replaces the factorisation inside the reference's

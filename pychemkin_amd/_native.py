@@ -139,6 +139,8 @@ PROTOTYPES = {
     "ckmi_equil_run": (ct.c_int, [_P, ct.POINTER(EquilCfg), ct.c_int32] + [_P] * 11),
     "ckmi_set_reactor_path": (ct.c_int, [ct.c_int32]),
     "ckmi_big_max_image_bytes": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32]),
+    "ckmi_reactor_variant": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_double, ct.c_int32, ct.c_int32,
+                                        ct.POINTER(ct.c_int32)]),
     "ckmi_set_rop_path": (ct.c_int, [ct.c_int32]),
     "ckmi_rop_jit_state": (ct.c_int, [_P, ct.POINTER(ct.c_int32)]),
     "ckmi_rop_jit_source": (ct.c_int, [ct.POINTER(MechDesc), ct.c_char_p, ct.c_int64, ct.POINTER(ct.c_int64)]),

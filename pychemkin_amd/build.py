@@ -21,7 +21,8 @@ DIFF_SRC = os.path.join(HERE, "csrc", "ckmi_diffusion.hip")  # binary / mixture-
 NET_SRC = os.path.join(HERE, "csrc", "ckmi_network.hip")  # PSR networks: flow balance, stream mixing, tear iteration
 TRAN_HDR = os.path.join(HERE, "csrc", "ckmi_transport.hpp")  # the ckmi_transport tables both transport units share
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("ckmi_device.hpp", "ckmi_reactor.hpp", "ckmi_image.hpp",
-                                                "ckmi_run.hpp", "ckmi_internal.hpp", "ckmi_reactor_kernel.hpp")] + [
+                                                "ckmi_run.hpp", "ckmi_internal.hpp", "ckmi_reactor_kernel.hpp",
+                                                "ckmi_dispatch.hpp")] + [
     os.path.join(HERE, "..", "include", "ckmi.h"), os.path.join(HERE, "..", "include", "ckmi_kin.h")]
 OUT = os.path.join(HERE, "_lib", "libckmi.so")
 OBJ_DIR = os.path.join(HERE, "_lib", "obj")

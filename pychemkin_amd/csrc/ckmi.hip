@@ -28,17 +28,6 @@ std::atomic<int> g_reactor_path{0};
 std::atomic<int> g_rop_path{0};
 constexpr int JIT_MIN_STATES = 16384;  // automatic choice: the specialised kernel from this batch size up
 
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_CHECK(x)                                                                   \
-  do {                                                                                 \
-    hipError_t _e = (x);                                                               \
-    if (_e != hipSuccess) return fail(CKMI_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 }  // namespace
 
 // the wave-per-reactor integrator kernel and its launcher (shared with ckmi_psr.hip)
@@ -337,8 +326,8 @@ template <typename T>
 int upload(ckmi_mech* m, const std::vector<T>& v, const T** out) {
   void* p = nullptr;
   size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
-  HIP_CHECK(hipMalloc(&p, bytes));
-  if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  CKMI_HIP_CHECK(hipMalloc(&p, bytes));
+  if (!v.empty()) CKMI_HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   m->allocs.push_back(p);
   *out = static_cast<const T*>(p);
   return CKMI_OK;
@@ -499,7 +488,7 @@ int build_image(ckmi_mech* m, const ckmi_mech_desc* d, const std::vector<int>& s
   const int KKp = (KK + 1 + WAVE - 1) / WAVE * WAVE;  // room for the dummy species slot
   const int sp_one = KKp - 1;                          // = SP_ONE (63) whenever KK <= 63
   if (KK > KK_IMAGE_MAX)
-    return fail(CKMI_ERR_UNSUPPORTED, "more than 255 species not supported by the mechanism image");
+    return set_error(CKMI_ERR_UNSUPPORTED, "more than 255 species not supported by the mechanism image");
   std::vector<uint32_t> urs(IIp, 0), ups(IIp, 0), unu(IIp, 0), uinfo(IIp, 0);
   std::vector<double> aux;
   int naux = 0;
@@ -525,7 +514,7 @@ int build_image(ckmi_mech* m, const ckmi_mech_desc* d, const std::vector<int>& s
         if (ns_p < 4) up[ns_p] = p4[u];
     }
     if (ns_r > 4 || ns_p > 4)
-      return fail(CKMI_ERR_UNSUPPORTED, "more than 4 molecules (sum of coefficients) on a reaction side");
+      return set_error(CKMI_ERR_UNSUPPORTED, "more than 4 molecules (sum of coefficients) on a reaction side");
     const uint8_t* pm = slots[s] >= 0 ? perm[slots[s]].data() : nullptr;
     for (int u = 0; u < ns_r; ++u) a |= (uint32_t)ur[pm ? pm[u] : u] << (8 * u);
     for (int u = 0; u < ns_p; ++u) b |= (uint32_t)up[pm ? pm[4 + u] : u] << (8 * u);
@@ -672,7 +661,7 @@ int build_image(ckmi_mech* m, const ckmi_mech_desc* d, const std::vector<int>& s
       }
     }
     const int o_el = put(el.data(), el.size() * 8);
-    if (o_el != I.o_e2t + 8 * E2T_N) return fail(CKMI_ERR_ARG, "image layout: element table not after e2t");
+    if (o_el != I.o_e2t + 8 * E2T_N) return set_error(CKMI_ERR_ARG, "image layout: element table not after e2t");
   }
   I.bytes = (int)blob.size();
   {
@@ -711,9 +700,9 @@ int build_image(ckmi_mech* m, const ckmi_mech_desc* d, const std::vector<int>& s
     I.jcol_ent = de;
   }
   void* p = nullptr;
-  HIP_CHECK(hipMalloc(&p, blob.size()));
+  CKMI_HIP_CHECK(hipMalloc(&p, blob.size()));
   m->allocs.push_back(p);
-  HIP_CHECK(hipMemcpy(p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+  CKMI_HIP_CHECK(hipMemcpy(p, blob.data(), blob.size(), hipMemcpyHostToDevice));
   I.blob = (const uint4*)p;
   return CKMI_OK;
 }
@@ -724,18 +713,17 @@ int launch_rop_n(const ckmi_mech* m, int n, const double* T, const double* P, co
   constexpr int NW = rop_waves(NCH);
   const size_t lds = (size_t)m->img.bytes + (size_t)NW * rop_slice_bytes(m->G, m->img.KK, m->img.KKp);
   int ncu = 0, per_cu = 0, lds_max = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, m->device));
-  HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
-  if (lds > (size_t)lds_max) return fail(CKMI_ERR_SIZE, "mechanism image + ROP work space exceed the LDS of a CU");
-  HIP_CHECK(hipFuncSetAttribute((const void*)rop_kernel<MODE, NCH, PL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rop_kernel<MODE, NCH, PL>, NW * WAVE, lds));
-  if (per_cu < 1) return fail(CKMI_ERR_SIZE, "ROP kernel does not fit on a CU");
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, m->device));
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
+  if (lds > (size_t)lds_max) return set_error(CKMI_ERR_SIZE, "mechanism image + ROP work space exceed the LDS of a CU");
+  if (int rc = raise_lds_limit(m->device, (const void*)rop_kernel<MODE, NCH, PL>, lds)) return rc;
+  CKMI_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rop_kernel<MODE, NCH, PL>, NW * WAVE, lds));
+  if (per_cu < 1) return set_error(CKMI_ERR_SIZE, "ROP kernel does not fit on a CU");
   const int tasks = (n + ROP_CHUNK - 1) / ROP_CHUNK;
   const int grid = std::max(1, std::min(ncu * per_cu, (tasks + NW - 1) / NW));
   hipLaunchKernelGGL((rop_kernel<MODE, NCH, PL>), dim3(grid), dim3(NW * WAVE), lds, stream, m->img, m->d.orig, n, T, P,
                      Y, o0, o1, o2);
-  HIP_CHECK(hipGetLastError());
+  CKMI_HIP_CHECK(hipGetLastError());
   return CKMI_OK;
 }
 
@@ -752,7 +740,7 @@ int launch_rop(const ckmi_mech* m, int n, const double* T, const double* P, cons
                       : launch_rop_n<MODE, 3, false>(m, n, T, P, Y, o0, o1, o2, stream);
     case 4: return pl ? launch_rop_n<MODE, 4, true>(m, n, T, P, Y, o0, o1, o2, stream)
                       : launch_rop_n<MODE, 4, false>(m, n, T, P, Y, o0, o1, o2, stream);
-    default: return fail(CKMI_ERR_UNSUPPORTED, "mechanism image with more than 255 species");
+    default: return set_error(CKMI_ERR_UNSUPPORTED, "mechanism image with more than 255 species");
   }
 }
 
@@ -773,19 +761,19 @@ struct DeviceScope {
 // compile and load the specialised ROP kernel of m once (thread-safe), on m's device; CKMI_OK when
 // it can run
 int jit_ready(ckmi_mech* m) {
-  if (!m->jit) return fail(CKMI_ERR_UNSUPPORTED, "no specialised ROP kernel");
+  if (!m->jit) return set_error(CKMI_ERR_UNSUPPORTED, "no specialised ROP kernel");
   JitRop& J = *m->jit;
   if (J.state.load() == 1) return CKMI_OK;
   std::lock_guard<std::mutex> lk(J.mu);
   if (J.state.load() == 1) return CKMI_OK;
-  if (J.state.load() == -1) return fail(CKMI_ERR_UNSUPPORTED, "specialised ROP kernel unavailable: " + J.why);
+  if (J.state.load() == -1) return set_error(CKMI_ERR_UNSUPPORTED, "specialised ROP kernel unavailable: " + J.why);
   std::vector<char> code;
   std::string log;
   const int rc = jit_rop_compile(J.src, code, log);
   if (rc) {
     J.why = "hipRTC compilation failed: " + log.substr(0, 2000);
     J.state.store(-1);
-    return fail(CKMI_ERR_HIP, J.why);
+    return set_error(CKMI_ERR_HIP, J.why);
   }
   DeviceScope on(m->device);
   if (hipModuleLoadData(&J.mod, code.data()) != hipSuccess ||
@@ -793,7 +781,7 @@ int jit_ready(ckmi_mech* m) {
           hipSuccess) {
     J.why = "hipModuleLoadData / hipModuleGetFunction failed";
     J.state.store(-1);
-    return fail(CKMI_ERR_HIP, J.why);
+    return set_error(CKMI_ERR_HIP, J.why);
   }
   J.state.store(1);
   return CKMI_OK;
@@ -801,7 +789,81 @@ int jit_ready(ckmi_mech* m) {
 
 }  // namespace
 
-int ckmi::set_error(int code, const std::string& msg) { return fail(code, msg); }
+int ckmi::set_error(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+
+// ---------------------------------------------------------------- the launch layer (ckmi_internal.hpp)
+int ckmi::stage_cfg(const DevCfg& dc, DevCfg* dst, hipStream_t stream) {
+  auto* hc = new DevCfg(dc);
+  const hipError_t e = hipMemcpyAsync(dst, hc, sizeof(DevCfg), hipMemcpyHostToDevice, stream);
+  if (e != hipSuccess) {
+    delete hc;
+    return set_error(CKMI_ERR_HIP, std::string("cfg copy: ") + hipGetErrorString(e));
+  }
+  CKMI_HIP_CHECK(hipLaunchHostFunc(stream, [](void* p) { delete static_cast<DevCfg*>(p); }, hc));
+  return CKMI_OK;
+}
+
+int ckmi::raise_lds_limit(int device, const void* fn, size_t bytes) {
+  if (bytes <= 64 * 1024) return CKMI_OK;
+  static thread_local std::map<std::pair<int, const void*>, size_t> limit;
+  size_t& set = limit[{device, fn}];
+  if (set < bytes) {
+    CKMI_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    set = bytes;
+  }
+  return CKMI_OK;
+}
+
+DevCfg ckmi::make_dev_cfg(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, bool integrate) {
+  DevCfg dc;  // the call's own configuration (staged per launch: no state shared between calls)
+  dc.c = *cfg;
+  if (dc.c.gfac == 0.0) dc.c.gfac = 1.0;
+  dc.ncrit = 0;
+  if (integrate) {  // the sorted union of the profiles' breakpoints in (0, t_end)
+    std::vector<double> tc;
+    for (int i = 0; i < cfg->nprof; ++i)
+      if (cfg->prof_t[i] > 0.0 && cfg->prof_t[i] < cfg->t_end) tc.push_back(cfg->prof_t[i]);
+    for (int i = 0; i < cfg->nprof2; ++i)
+      if (cfg->prof2_t[i] > 0.0 && cfg->prof2_t[i] < cfg->t_end) tc.push_back(cfg->prof2_t[i]);
+    for (int i = 0; i < cfg->nprof3; ++i)
+      if (cfg->prof3_t[i] > 0.0 && cfg->prof3_t[i] < cfg->t_end) tc.push_back(cfg->prof3_t[i]);
+    std::sort(tc.begin(), tc.end());
+    tc.erase(std::unique(tc.begin(), tc.end()), tc.end());
+    dc.ncrit = (int)tc.size();
+    std::copy(tc.begin(), tc.end(), dc.tcrit);
+  }
+  dc.guard_y = std::max(1e-3, 1e3 * cfg->atol);
+  dc.guard_tlo = m->tguard_lo;
+  dc.guard_thi = m->tguard_hi;
+  dc.npe = (integrate && !cfg->no_elem_proj) ? m->npe : 0;
+  return dc;
+}
+
+int ckmi::check_reactor_cfg(const ckmi_reactor_cfg* cfg, const ckmi_reactor_ext* ext, bool profiles) {
+  if (cfg->energy != 1 && cfg->energy != 2) return set_error(CKMI_ERR_ARG, "energy must be 1 or 2");
+  if (!(cfg->gfac >= 0.0)) return set_error(CKMI_ERR_ARG, "GFAC must be >= 0");
+  if (!(cfg->htc >= 0.0) || !(cfg->areaq >= 0.0) || !(cfg->tamb > 0.0 || cfg->htc * cfg->areaq == 0.0))
+    return set_error(CKMI_ERR_ARG, "HTC, AREAQ must be >= 0 and TAMB > 0");
+  if (ext && (ext->afac_rxn != nullptr) != (ext->afac != nullptr))
+    return set_error(CKMI_ERR_ARG, "afac_rxn and afac go together");
+  if (!profiles) return CKMI_OK;
+  if (cfg->nprof < 0 || cfg->nprof > 64) return set_error(CKMI_ERR_ARG, "nprof must be in [0, 64]");
+  if (cfg->nprof2 < 0 || cfg->nprof2 > 64) return set_error(CKMI_ERR_ARG, "nprof2 must be in [0, 64]");
+  if (cfg->nprof3 < 0 || cfg->nprof3 > 64) return set_error(CKMI_ERR_ARG, "nprof3 must be in [0, 64]");
+  if (cfg->prof_kind != 0 && cfg->prof_kind != 1)
+    return set_error(CKMI_ERR_ARG, "prof_kind must be 0 (VPRO/PPRO) or 1 (TPRO)");
+  if (cfg->prof_kind == 1 && cfg->energy != 2)
+    return set_error(CKMI_ERR_ARG, "TPRO needs a given-temperature run (energy = 2)");
+  if (cfg->nprof2 > 0 && cfg->prof2_kind != 1 && cfg->prof2_kind != 2)
+    return set_error(CKMI_ERR_ARG, "prof2_kind must be 1 (QPRO) or 2 (AEXT)");
+  if (cfg->nprof2 > 0 && cfg->energy != 1) return set_error(CKMI_ERR_ARG, "QPRO / AEXT need an energy-equation run");
+  if (cfg->nprof3 > 0 && !(cfg->nprof2 > 0 && cfg->prof2_kind == 1))
+    return set_error(CKMI_ERR_ARG, "the third profile (AEXT) needs a QPRO second profile");
+  return CKMI_OK;
+}
 
 extern "C" {
 
@@ -810,25 +872,25 @@ const char* ckmi_last_error(void) { return g_err.c_str(); }
 #ifdef CKMI_PHASE_TIMERS
 // diagnostic build only: buf = device u64 [n][8] (rhs, jac, lu, solve, total cycles)
 int ckmi_debug_phase_buffer(void* buf) {
-  HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_buf), &buf, sizeof(buf)));
+  CKMI_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_buf), &buf, sizeof(buf)));
   return CKMI_OK;
 }
 #endif
 int ckmi_version(void) { return CKMI_ABI_VERSION; }
 
 int ckmi_mech_create(const ckmi_mech_desc* d, ckmi_mech** out) {
-  if (!d || !out) return fail(CKMI_ERR_ARG, "null argument");
+  if (!d || !out) return set_error(CKMI_ERR_ARG, "null argument");
   const int KK = d->KK, II = d->II;
-  if (KK <= 0 || II < 0) return fail(CKMI_ERR_SIZE, "bad sizes");
-  if (KK > KK_IMAGE_MAX) return fail(CKMI_ERR_UNSUPPORTED, "more than 255 species not supported by this build");
+  if (KK <= 0 || II < 0) return set_error(CKMI_ERR_SIZE, "bad sizes");
+  if (KK > KK_IMAGE_MAX) return set_error(CKMI_ERR_UNSUPPORTED, "more than 255 species not supported by this build");
   // slot counts and species indices first: everything below (rxn_general, the slot classes, the
   // image) reads [4 i + u] for u < nr[i] / np[i]
-  if (const char* bad = ckmi::check_slots(d)) return fail(CKMI_ERR_ARG, bad);
+  if (const char* bad = ckmi::check_slots(d)) return set_error(CKMI_ERR_ARG, bad);
   auto* m = new ckmi_mech();
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) {
     delete m;
-    return fail(CKMI_ERR_HIP, "no HIP device");
+    return set_error(CKMI_ERR_HIP, "no HIP device");
   }
   m->device = dev;
   m->KK = KK;
@@ -866,7 +928,7 @@ int ckmi_mech_create(const ckmi_mech_desc* d, ckmi_mech** out) {
   for (int i = 0; i < II; ++i) {
     if (d->rtype[i] < 0 || d->rtype[i] > CKMI_RXN_LT) {
       delete m;
-      return fail(CKMI_ERR_UNSUPPORTED, "unsupported reaction type");
+      return set_error(CKMI_ERR_UNSUPPORTED, "unsupported reaction type");
     }
     if (d->rtype[i] == CKMI_RXN_CHEB) {
       const int p0 = d->plog_ptr ? d->plog_ptr[i] : 0, nrow = d->plog_ptr ? d->plog_ptr[i + 1] - p0 : 0;
@@ -876,7 +938,7 @@ int ckmi_mech_create(const ckmi_mech_desc* d, ckmi_mech** out) {
                       r[4] > 0.0 && r[5] > r[4] && r[6] > 0.0 && r[7] > r[6] && !d->has_rev[i];
       if (!ok) {
         delete m;
-        return fail(CKMI_ERR_UNSUPPORTED, "Chebyshev record must hold 1..12 x 1..12 coefficients, increasing "
+        return set_error(CKMI_ERR_UNSUPPORTED, "Chebyshev record must hold 1..12 x 1..12 coefficients, increasing "
                                           "positive ranges and no REV");
       }
     }
@@ -886,7 +948,7 @@ int ckmi_mech_create(const ckmi_mech_desc* d, ckmi_mech** out) {
       for (int j = 0; ok && j + 1 < n; ++j) ok = d->plog_par[4 * (p0 + j)] < d->plog_par[4 * (p0 + j + 1)];
       if (!ok) {
         delete m;
-        return fail(CKMI_ERR_UNSUPPORTED, "PLOG table must hold 1..64 points with ascending pressures and no REV");
+        return set_error(CKMI_ERR_UNSUPPORTED, "PLOG table must hold 1..64 points with ascending pressures and no REV");
       }
     }
   }
@@ -956,24 +1018,24 @@ int ckmi_mech_create(const ckmi_mech_desc* d, ckmi_mech** out) {
     if (rxn_general(d, i)) {  // FORD / RORD / non-integral: real coefficients, extended variants
       if (type == CKMI_RXN_PLOG || lt) {
         delete m;
-        return fail(CKMI_ERR_UNSUPPORTED,
+        return set_error(CKMI_ERR_UNSUPPORTED,
                     "FORD / RORD or non-integral coefficients on a PLOG, Chebyshev or Landau-Teller reaction");
       }
       for (int u = 0; u < nr; ++u)
         if (!(d->rnu[i * CKMI_SLOTS + u] > 0.0) || (d->ford && d->ford[i * CKMI_SLOTS + u] < 0.0)) {
           delete m;
-          return fail(CKMI_ERR_UNSUPPORTED, "stoichiometric coefficients must be > 0 and orders >= 0");
+          return set_error(CKMI_ERR_UNSUPPORTED, "stoichiometric coefficients must be > 0 and orders >= 0");
         }
       for (int u = 0; u < np; ++u)
         if (!(d->pnu[i * CKMI_SLOTS + u] > 0.0) || (d->rord && d->rord[i * CKMI_SLOTS + u] < 0.0)) {
           delete m;
-          return fail(CKMI_ERR_UNSUPPORTED, "stoichiometric coefficients must be > 0 and orders >= 0");
+          return set_error(CKMI_ERR_UNSUPPORTED, "stoichiometric coefficients must be > 0 and orders >= 0");
         }
       flags[s] |= RX_GEN;
     }
     if (nr > GEN_SLOTS || np > GEN_SLOTS || ((nr > SLOTS || np > SLOTS) && !(flags[s] & RX_GEN))) {
       delete m;
-      return fail(CKMI_ERR_UNSUPPORTED, "more than 8 species on a reaction side");
+      return set_error(CKMI_ERR_UNSUPPORTED, "more than 8 species on a reaction side");
     }
     nrp[s] = nr | (np << 8);
     int rr[4] = {0, 0, 0, 0}, pp[4] = {0, 0, 0, 0};
@@ -1113,14 +1175,14 @@ int ckmi_mech_destroy(ckmi_mech* m) {
 }
 
 int ckmi_mech_sizes(const ckmi_mech* m, int32_t* KK, int32_t* II) {
-  if (!m) return fail(CKMI_ERR_ARG, "null mech");
+  if (!m) return set_error(CKMI_ERR_ARG, "null mech");
   if (KK) *KK = m->KK;
   if (II) *II = m->II;
   return CKMI_OK;
 }
 
 int ckmi_get_arrhenius(const ckmi_mech* m, double* A, double* b, double* E) {
-  if (!m) return fail(CKMI_ERR_ARG, "null mech");
+  if (!m) return set_error(CKMI_ERR_ARG, "null mech");
   for (int i = 0; i < m->II; ++i) {
     if (A) A[i] = std::exp(m->lnA_orig[i]);
     if (b) b[i] = m->b_orig[i];
@@ -1130,43 +1192,43 @@ int ckmi_get_arrhenius(const ckmi_mech* m, double* A, double* b, double* E) {
 }
 
 int ckmi_reaction_slots(const ckmi_mech* m, int32_t* slot) {
-  if (!m || !slot) return fail(CKMI_ERR_ARG, "null mech or slot array");
+  if (!m || !slot) return set_error(CKMI_ERR_ARG, "null mech or slot array");
   for (int i = 0; i < m->II; ++i) slot[i] = m->slot_of[i];
   return CKMI_OK;
 }
 
 int ckmi_set_afactor(ckmi_mech* m, int32_t irxn, double A) {
-  if (!m || irxn < 0 || irxn >= m->II || !(A > 0.0)) return fail(CKMI_ERR_ARG, "bad reaction index or A");
+  if (!m || irxn < 0 || irxn >= m->II || !(A > 0.0)) return set_error(CKMI_ERR_ARG, "bad reaction index or A");
   if (m->rtype_orig[irxn] == CKMI_RXN_PLOG || m->rtype_orig[irxn] == CKMI_RXN_CHEB)
-    return fail(CKMI_ERR_UNSUPPORTED, "A-factor of a PLOG / Chebyshev reaction (its rate comes from its table)");
+    return set_error(CKMI_ERR_UNSUPPORTED, "A-factor of a PLOG / Chebyshev reaction (its rate comes from its table)");
   const double lnA = std::log(A);
   m->lnA_orig[irxn] = lnA;
   const int s = m->slot_of[irxn];
-  HIP_CHECK(hipMemcpy(const_cast<double*>(m->d.lnA) + s, &lnA, sizeof(double), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy((char*)m->img.blob + m->img.o_lnA + sizeof(double) * s, &lnA, sizeof(double),
+  CKMI_HIP_CHECK(hipMemcpy(const_cast<double*>(m->d.lnA) + s, &lnA, sizeof(double), hipMemcpyHostToDevice));
+  CKMI_HIP_CHECK(hipMemcpy((char*)m->img.blob + m->img.o_lnA + sizeof(double) * s, &lnA, sizeof(double),
                       hipMemcpyHostToDevice));
   if (m->jit && m->jit->prm) {
-    HIP_CHECK(hipMemcpy(m->jit->prm + m->jit->lnA_off[irxn], &lnA, sizeof(double), hipMemcpyHostToDevice));
+    CKMI_HIP_CHECK(hipMemcpy(m->jit->prm + m->jit->lnA_off[irxn], &lnA, sizeof(double), hipMemcpyHostToDevice));
     if (m->b_orig[irxn] == 0.0 && m->E_orig[irxn] == 0.0)  // k = A reactions read A itself (ckmi_jit.cpp)
-      HIP_CHECK(hipMemcpy(m->jit->prm + m->jit->lnA_off[irxn] + 1, &A, sizeof(double), hipMemcpyHostToDevice));
+      CKMI_HIP_CHECK(hipMemcpy(m->jit->prm + m->jit->lnA_off[irxn] + 1, &A, sizeof(double), hipMemcpyHostToDevice));
   }
   return CKMI_OK;
 }
 
 int ckmi_species_thermo(const ckmi_mech* m, int32_t n, const double* T, double* cp_R, double* h_RT, double* s_R,
                         void* stream) {
-  if (!m || n < 0) return fail(CKMI_ERR_ARG, "bad argument");
+  if (!m || n < 0) return set_error(CKMI_ERR_ARG, "bad argument");
   if (n == 0) return CKMI_OK;
   const int bs = 256;
   hipLaunchKernelGGL(species_thermo_kernel, dim3((n + bs - 1) / bs), dim3(bs), 0, (hipStream_t)stream, m->d, n, T, cp_R,
                      h_RT, s_R);
-  HIP_CHECK(hipGetLastError());
+  CKMI_HIP_CHECK(hipGetLastError());
   return CKMI_OK;
 }
 
 int ckmi_rop_thermo(const ckmi_mech* m, int32_t n, const double* T, const double* P, const double* Y, double* wdot,
                     double* cp, double* h, void* stream) {
-  if (!m || n < 0 || !wdot) return fail(CKMI_ERR_ARG, "bad argument");
+  if (!m || n < 0 || !wdot) return set_error(CKMI_ERR_ARG, "bad argument");
   if (n == 0) return CKMI_OK;
   const int path = g_rop_path.load();
   if (path == 2 || (path == 0 && n >= JIT_MIN_STATES)) {
@@ -1174,7 +1236,7 @@ int ckmi_rop_thermo(const ckmi_mech* m, int32_t n, const double* T, const double
     if (rc == CKMI_OK) {
       DeviceScope on(m->device);
       void* args[] = {&n, (void*)&T, (void*)&P, (void*)&Y, &wdot, &cp, &h, &m->jit->prm};
-      HIP_CHECK(hipModuleLaunchKernel(m->jit->fn, (unsigned)((n + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)stream,
+      CKMI_HIP_CHECK(hipModuleLaunchKernel(m->jit->fn, (unsigned)((n + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)stream,
                                       args, nullptr));
       return CKMI_OK;
     }
@@ -1184,17 +1246,17 @@ int ckmi_rop_thermo(const ckmi_mech* m, int32_t n, const double* T, const double
 }
 
 int ckmi_set_rop_path(int32_t path) {
-  if (path < 0 || path > 2) return fail(CKMI_ERR_ARG, "rop path must be 0 (auto), 1 (generic) or 2 (specialised)");
+  if (path < 0 || path > 2) return set_error(CKMI_ERR_ARG, "rop path must be 0 (auto), 1 (generic) or 2 (specialised)");
   g_rop_path = path;
   return CKMI_OK;
 }
 
 int ckmi_rop_jit_source(const ckmi_mech_desc* d, char* buf, int64_t cap, int64_t* len) {
-  if (!d || !len) return fail(CKMI_ERR_ARG, "null argument");
+  if (!d || !len) return set_error(CKMI_ERR_ARG, "null argument");
   std::string src, why;
   std::vector<double> prm;
   std::vector<int> off;
-  if (!jit_rop_generate(d, src, prm, off, why)) return fail(CKMI_ERR_UNSUPPORTED, why);
+  if (!jit_rop_generate(d, src, prm, off, why)) return set_error(CKMI_ERR_UNSUPPORTED, why);
   *len = (int64_t)src.size();
   if (buf && cap > 0) {
     const size_t k = std::min<size_t>((size_t)cap - 1, src.size());
@@ -1205,19 +1267,19 @@ int ckmi_rop_jit_source(const ckmi_mech_desc* d, char* buf, int64_t cap, int64_t
 }
 
 int ckmi_rop_jit_compile(const ckmi_mech_desc* d, int64_t* code_bytes) {
-  if (!d || !code_bytes) return fail(CKMI_ERR_ARG, "null argument");
+  if (!d || !code_bytes) return set_error(CKMI_ERR_ARG, "null argument");
   std::string src, why, log;
   std::vector<double> prm;
   std::vector<int> off;
-  if (!jit_rop_generate(d, src, prm, off, why)) return fail(CKMI_ERR_UNSUPPORTED, why);
+  if (!jit_rop_generate(d, src, prm, off, why)) return set_error(CKMI_ERR_UNSUPPORTED, why);
   std::vector<char> code;
-  if (jit_rop_compile(src, code, log)) return fail(CKMI_ERR_HIP, "hipRTC compilation failed: " + log.substr(0, 2000));
+  if (jit_rop_compile(src, code, log)) return set_error(CKMI_ERR_HIP, "hipRTC compilation failed: " + log.substr(0, 2000));
   *code_bytes = (int64_t)code.size();
   return CKMI_OK;
 }
 
 int ckmi_rop_jit_state(const ckmi_mech* m, int32_t* state) {
-  if (!m || !state) return fail(CKMI_ERR_ARG, "null argument");
+  if (!m || !state) return set_error(CKMI_ERR_ARG, "null argument");
   *state = m->jit ? m->jit->state.load() : -1;
   if (*state == -1 && m->jit) {
     std::lock_guard<std::mutex> lk(m->jit->mu);
@@ -1228,234 +1290,179 @@ int ckmi_rop_jit_state(const ckmi_mech* m, int32_t* state) {
 
 int ckmi_reaction_rates(const ckmi_mech* m, int32_t n, const double* T, const double* P, const double* Y, double* qf,
                         double* qr, void* stream) {
-  if (!m || n < 0 || !qf || !qr) return fail(CKMI_ERR_ARG, "bad argument");
+  if (!m || n < 0 || !qf || !qr) return set_error(CKMI_ERR_ARG, "bad argument");
   if (n == 0) return CKMI_OK;
   return launch_rop<1>(m, n, T, P, Y, qf, qr, nullptr, (hipStream_t)stream);
 }
+
+namespace {
+// The closed-reactor instantiations, named in the order the code object has always held them.  Kernels are laid
+// out in the order they are first named; it is fixed here, not left to the order the chooser's visitor happens to
+// name them in, so that a change to the host code leaves the device code object byte for byte as it was (which is
+// how such a change is checked: profiles/launch_layer_kernel_resources.txt).
+#ifndef CKMI_PROBE_C3
+[[maybe_unused]] constexpr int (*REACTOR_VARIANTS[])(const ckmi_mech*, int, const DevCfg&, const ReactorIO&, hipStream_t,
+                                                      int) = {
+    launch_reactors<64, true, true>, launch_reactors<64, true, false>,  launch_reactors<54, false, true>,
+    launch_reactors<32>,             launch_reactors<54, false, false>, launch_reactors<64, false, true>,
+    launch_reactors<64, false, false>};
+#endif
+}  // namespace
 
 int ckmi_reactor_run_ex(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, int32_t n, const int32_t* problem,
                         const double* T0, const double* P0, const double* V0, const double* Y0,
                         const ckmi_reactor_ext* ext, double* tau, double* Tend, double* Pend, double* Vend,
                         double* Yend, int32_t* stats, int32_t nsave, const double* t_save, double* y_save,
                         void* stream) {
-  if (!m || !cfg || n < 0) return fail(CKMI_ERR_ARG, "bad argument");
-  if (cfg->nprof < 0 || cfg->nprof > 64) return fail(CKMI_ERR_ARG, "nprof must be in [0, 64]");
-  if (!(cfg->t_end > 0.0) || !(cfg->rtol > 0.0) || !(cfg->atol > 0.0)) return fail(CKMI_ERR_ARG, "t_end, rtol, atol must be > 0");
-  if (cfg->energy != 1 && cfg->energy != 2) return fail(CKMI_ERR_ARG, "energy must be 1 or 2");
-  if (cfg->ign_mode < 0 || cfg->ign_mode > 4) return fail(CKMI_ERR_ARG, "bad ignition mode");
-  if (cfg->ign_mode == 4 && (cfg->ign_species < 0 || cfg->ign_species >= m->KK)) return fail(CKMI_ERR_ARG, "bad KLIM species");
-  if (cfg->prof_kind != 0 && cfg->prof_kind != 1) return fail(CKMI_ERR_ARG, "prof_kind must be 0 (VPRO/PPRO) or 1 (TPRO)");
-  if (cfg->prof_kind == 1 && cfg->energy != 2) return fail(CKMI_ERR_ARG, "TPRO needs a given-temperature run (energy = 2)");
-  if (!(cfg->gfac >= 0.0)) return fail(CKMI_ERR_ARG, "GFAC must be >= 0");
-  if (!(cfg->htc >= 0.0) || !(cfg->areaq >= 0.0) || !(cfg->tamb > 0.0 || cfg->htc * cfg->areaq == 0.0))
-    return fail(CKMI_ERR_ARG, "HTC, AREAQ must be >= 0 and TAMB > 0");
-  if (cfg->asteps < 0) return fail(CKMI_ERR_ARG, "asteps must be >= 0");
-  if (nsave > 0 && (!t_save || !y_save)) return fail(CKMI_ERR_ARG, "t_save / y_save required when nsave > 0");
-  if (ext && (ext->afac_rxn != nullptr) != (ext->afac != nullptr)) return fail(CKMI_ERR_ARG, "afac_rxn and afac go together");
+  if (!m || !cfg || n < 0) return set_error(CKMI_ERR_ARG, "bad argument");
+  if (int rc = check_reactor_cfg(cfg, ext, true)) return rc;
+  if (!(cfg->t_end > 0.0) || !(cfg->rtol > 0.0) || !(cfg->atol > 0.0)) return set_error(CKMI_ERR_ARG, "t_end, rtol, atol must be > 0");
+  if (cfg->ign_mode < 0 || cfg->ign_mode > 4) return set_error(CKMI_ERR_ARG, "bad ignition mode");
+  if (cfg->ign_mode == 4 && (cfg->ign_species < 0 || cfg->ign_species >= m->KK)) return set_error(CKMI_ERR_ARG, "bad KLIM species");
+  if (cfg->asteps < 0) return set_error(CKMI_ERR_ARG, "asteps must be >= 0");
+  if (nsave > 0 && (!t_save || !y_save)) return set_error(CKMI_ERR_ARG, "t_save / y_save required when nsave > 0");
   if (ext && ext->n_adap && (ext->max_adap <= 0 || !ext->t_adap || !ext->y_adap))
-    return fail(CKMI_ERR_ARG, "n_adap needs max_adap > 0, t_adap and y_adap");
-  if (cfg->nprof2 < 0 || cfg->nprof2 > 64) return fail(CKMI_ERR_ARG, "nprof2 must be in [0, 64]");
-  if (cfg->nprof2 > 0 && cfg->prof2_kind != 1 && cfg->prof2_kind != 2)
-    return fail(CKMI_ERR_ARG, "prof2_kind must be 1 (QPRO) or 2 (AEXT)");
-  if (cfg->nprof2 > 0 && cfg->energy != 1) return fail(CKMI_ERR_ARG, "QPRO / AEXT need an energy-equation run");
-  if (cfg->nprof3 < 0 || cfg->nprof3 > 64) return fail(CKMI_ERR_ARG, "nprof3 must be in [0, 64]");
-  if (cfg->nprof3 > 0 && !(cfg->nprof2 > 0 && cfg->prof2_kind == 1))
-    return fail(CKMI_ERR_ARG, "the third profile (AEXT) needs a QPRO second profile");
-  if (cfg->avar > m->KK || cfg->avar < -1) return fail(CKMI_ERR_ARG, "avar must be -1, 0 (T) or 1 + species index");
+    return set_error(CKMI_ERR_ARG, "n_adap needs max_adap > 0, t_adap and y_adap");
+  if (cfg->avar > m->KK || cfg->avar < -1) return set_error(CKMI_ERR_ARG, "avar must be -1, 0 (T) or 1 + species index");
   if (cfg->eng[CKMI_ENG_HTMODEL] == 1.0 && !cfg->tran)
-    return fail(CKMI_ERR_ARG, "the engine's ICHX heat transfer needs the transport fits (cfg->tran)");
+    return set_error(CKMI_ERR_ARG, "the engine's ICHX heat transfer needs the transport fits (cfg->tran)");
   if (n == 0) return CKMI_OK;
-  DevCfg dc;  // this call's configuration (staged per launch: no state shared between calls)
-  {
-    dc.c = *cfg;
-    if (dc.c.gfac == 0.0) dc.c.gfac = 1.0;
-    std::vector<double> tc;
-    for (int i = 0; i < cfg->nprof; ++i)
-      if (cfg->prof_t[i] > 0.0 && cfg->prof_t[i] < cfg->t_end) tc.push_back(cfg->prof_t[i]);
-    for (int i = 0; i < cfg->nprof2; ++i)
-      if (cfg->prof2_t[i] > 0.0 && cfg->prof2_t[i] < cfg->t_end) tc.push_back(cfg->prof2_t[i]);
-    for (int i = 0; i < cfg->nprof3; ++i)
-      if (cfg->prof3_t[i] > 0.0 && cfg->prof3_t[i] < cfg->t_end) tc.push_back(cfg->prof3_t[i]);
-    std::sort(tc.begin(), tc.end());
-    tc.erase(std::unique(tc.begin(), tc.end()), tc.end());
-    dc.ncrit = (int)tc.size();
-    std::copy(tc.begin(), tc.end(), dc.tcrit);
-    dc.guard_y = std::max(1e-3, 1e3 * cfg->atol);
-    dc.guard_tlo = m->tguard_lo;
-    dc.guard_thi = m->tguard_hi;
-    dc.npe = cfg->no_elem_proj ? 0 : m->npe;
-  }
+  const DevCfg dc = make_dev_cfg(m, cfg, true);
   ReactorIO io{problem, T0, P0, V0, Y0, tau, Tend, Pend, Vend, Yend, stats, nsave, t_save, y_save,
                ext ? ext->afac_rxn : nullptr, ext ? ext->afac : nullptr, ext ? ext->max_adap : 0,
                ext ? ext->t_adap : nullptr, ext ? ext->y_adap : nullptr, ext ? ext->n_adap : nullptr,
                ext ? ext->t_stop : nullptr};
   const int nvar = m->KK + 1;
-  int rc;
-  // PLOG mechanisms use one (64-wide) reactor variant, so that the PLOG branch costs compile time once
-  // more than 63 species: one workgroup per reactor (ckmi_big.hip); else one wave per reactor, its
-  // Newton inverse stored in FP64 when the tolerances ask for more than its FP32 rounding resolves
-  // (rtol < 1e-9; measured: the FP32-stored inverse integrates the rtol = 1e-8 sweeps of configs[2]
-  // and [3] without a failure, and fails one of 55 reactors at rtol = 1e-10, atol = 1e-20), and for
-  // mechanisms with FORD / RORD / fractional orders, whose d C^o / dC = o C^(o-1) grows without
-  // bound as C -> 0 (the FP32-stored inverse of such a Newton matrix stalled one reactor of five)
   const int rpath = g_reactor_path.load();
-  const bool f64 = rpath == 2 || (rpath != 3 && (cfg->rtol < 1e-9 || m->has_general));
   const hipStream_t st = (hipStream_t)stream;
-  // An FP32-inverse launch skips the plug-flow reactors and an FP64-inverse launch of the same size
-  // follows it for them (it pulls and drops the other indices: ~0.1 ms per 65,536 reactors when
-  // there are none); the problem array is device memory, so the host cannot tell in advance.
-  const int no_pf = SEL_NO_PFR;
-  // the automatic choice lets the FP64-inverse launch of the 64-wide variants also take again what the FP32-inverse
-  // launch failed on (error test, convergence); a forced path (3) keeps the FP32 inverse's own status
-  const int pf_sel = rpath == 0 ? SEL_PFR_RETRY : SEL_PFR;
-  if (nvar > 64 || rpath == 1) {
+  int rc = CKMI_OK;
+  // more than 63 species: one workgroup per reactor (ckmi_big.hip); else one wave per reactor
+  if (use_workgroup_kernel(nvar, rpath)) {
     // the workgroup kernel has no engine model: checked on the host (one synchronous copy of problem[])
     std::vector<int32_t> hp(n);
-    HIP_CHECK(hipMemcpyAsync(hp.data(), problem, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    CKMI_HIP_CHECK(hipMemcpyAsync(hp.data(), problem, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    CKMI_HIP_CHECK(hipStreamSynchronize(st));
     if (std::find(hp.begin(), hp.end(), 4) != hp.end())
-      return fail(CKMI_ERR_UNSUPPORTED, "engine reactors (problem 4) need KK + 1 <= 64 (the wave-per-reactor kernel)");
+      return set_error(CKMI_ERR_UNSUPPORTED, "engine reactors (problem 4) need KK + 1 <= 64 (the wave-per-reactor kernel)");
     rc = launch_big_reactors(m, n, dc, io, st);
-  }
-#ifdef CKMI_PROBE_C3
-  // ISA probe build (scripts/isa_probe.sh): only the configs[2] kernel is instantiated, so that its
-  // register / scratch figures come out of a one-variant compile; never linked into libckmi.so
-  else rc = launch_reactors<54>(m, n, dc, io, st, no_pf);
-#else
-  else if (m->has_plog) {
-    rc = f64 ? launch_reactors<64, true, true>(m, n, dc, io, st) : launch_reactors<64, true>(m, n, dc, io, st, no_pf);
-    if (!rc && !f64) rc = launch_reactors<64, true, true>(m, n, dc, io, st, pf_sel);
-  } else if (nvar <= 54) {
-    if (f64) rc = launch_reactors<54, false, true>(m, n, dc, io, st);
-    else {
-      rc = nvar <= 32 ? launch_reactors<32>(m, n, dc, io, st, no_pf) : launch_reactors<54>(m, n, dc, io, st, no_pf);
-      if (!rc) rc = launch_reactors<54, false, true>(m, n, dc, io, st, SEL_PFR);
-    }
   } else {
-    rc = f64 ? launch_reactors<64, false, true>(m, n, dc, io, st) : launch_reactors<64>(m, n, dc, io, st, no_pf);
-    if (!rc && !f64) rc = launch_reactors<64, false, true>(m, n, dc, io, st, pf_sel);
+    // An FP32-inverse launch skips the plug-flow reactors and an FP64-inverse launch of the same size
+    // follows it for them (it pulls and drops the other indices: ~0.1 ms per 65,536 reactors when
+    // there are none); the problem array is device memory, so the host cannot tell in advance.
+    const WavePlan p = wave_plan(nvar, m->has_plog, m->has_general, cfg->rtol, rpath, false);
+    if (p.n32)
+      rc = visit_wave_variant<false>(p.n32, p.pl, [&](auto N, auto PL) {
+        return launch_reactors<decltype(N)::value, decltype(PL)::value, false>(m, n, dc, io, st, SEL_NO_PFR);
+      });
+    if (!rc)
+      rc = visit_wave_variant<true>(p.n64, p.pl, [&](auto N, auto PL) {
+        return launch_reactors<decltype(N)::value, decltype(PL)::value, true>(m, n, dc, io, st, f64_sel(p.f64_takes));
+      });
   }
-#endif
   if (rc) return rc;
-  HIP_CHECK(hipGetLastError());
+  CKMI_HIP_CHECK(hipGetLastError());
   return CKMI_OK;
 }
 
 int ckmi_engine_heat_rates(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, double T0, double P0, const double* Y0,
                            int32_t n, const double* t, const double* y, double* ahrr, double* qloss, void* stream) {
-  if (!m || !cfg || n < 0 || !Y0 || (n > 0 && (!t || !y || !ahrr || !qloss))) return fail(CKMI_ERR_ARG, "bad argument");
-  if (!(T0 > 0.0) || !(P0 > 0.0)) return fail(CKMI_ERR_ARG, "T0 and P0 must be > 0");
-  if (m->KK + 1 > WAVE) return fail(CKMI_ERR_UNSUPPORTED, "engine heat rates need KK + 1 <= 64 (as engine runs)");
+  if (!m || !cfg || n < 0 || !Y0 || (n > 0 && (!t || !y || !ahrr || !qloss))) return set_error(CKMI_ERR_ARG, "bad argument");
+  if (!(T0 > 0.0) || !(P0 > 0.0)) return set_error(CKMI_ERR_ARG, "T0 and P0 must be > 0");
+  if (m->KK + 1 > WAVE) return set_error(CKMI_ERR_UNSUPPORTED, "engine heat rates need KK + 1 <= 64 (as engine runs)");
   if (cfg->eng[CKMI_ENG_HTMODEL] == 1.0 && !cfg->tran)
-    return fail(CKMI_ERR_ARG, "the engine's ICHX heat transfer needs the transport fits (cfg->tran)");
+    return set_error(CKMI_ERR_ARG, "the engine's ICHX heat transfer needs the transport fits (cfg->tran)");
   if (n == 0) return CKMI_OK;
-  DevCfg dc;
-  dc.c = *cfg;
-  if (dc.c.gfac == 0.0) dc.c.gfac = 1.0;
-  dc.ncrit = 0;
-  dc.guard_y = std::max(1e-3, 1e3 * cfg->atol);
-  dc.guard_tlo = m->tguard_lo;
-  dc.guard_thi = m->tguard_hi;
-  dc.npe = 0;  // (no integration)
+  const DevCfg dc = make_dev_cfg(m, cfg, false);
   const hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)align16(m->img.bytes) + slice_vec_bytes(m->G) + align16((int)sizeof(RunCtx));
   const void* fn = m->has_plog ? (const void*)engine_heat_kernel<true> : (const void*)engine_heat_kernel<false>;
-  if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const size_t cbytes = (sizeof(DevCfg) + 255) & ~(size_t)255;
-  void* ws = nullptr;
-  HIP_CHECK(hipMallocAsync(&ws, cbytes, st));
-  int rc = stage_cfg(dc, (DevCfg*)ws, st);
-  if (rc == CKMI_OK) {
-    const int grid = std::min(n, 4096);
-    if (m->has_plog)
-      hipLaunchKernelGGL(engine_heat_kernel<true>, dim3(grid), dim3(WAVE), lds, st, m->img, (const DevCfg*)ws, T0, P0,
-                         Y0, n, t, y, ahrr, qloss);
-    else
-      hipLaunchKernelGGL(engine_heat_kernel<false>, dim3(grid), dim3(WAVE), lds, st, m->img, (const DevCfg*)ws, T0, P0,
-                         Y0, n, t, y, ahrr, qloss);
-    HIP_CHECK(hipGetLastError());
-  }
-  HIP_CHECK(hipFreeAsync(ws, st));
-  return rc;
+  if (int rc = raise_lds_limit(m->device, fn, lds)) return rc;
+  const size_t cbytes = StreamWorkspace::aligned(sizeof(DevCfg));
+  StreamWorkspace ws(st);
+  if (int rc = ws.alloc(cbytes)) return rc;
+  DevCfg* dcfg = ws.take<DevCfg>(cbytes);
+  if (int rc = stage_cfg(dc, dcfg, st)) return rc;
+  const int grid = std::min(n, 4096);
+  if (m->has_plog)
+    hipLaunchKernelGGL(engine_heat_kernel<true>, dim3(grid), dim3(WAVE), lds, st, m->img, (const DevCfg*)dcfg, T0, P0,
+                       Y0, n, t, y, ahrr, qloss);
+  else
+    hipLaunchKernelGGL(engine_heat_kernel<false>, dim3(grid), dim3(WAVE), lds, st, m->img, (const DevCfg*)dcfg, T0, P0,
+                       Y0, n, t, y, ahrr, qloss);
+  CKMI_HIP_CHECK(hipGetLastError());
+  return CKMI_OK;
 }
 
 int ckmi_reactor_rhs_jac(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, int32_t n, const int32_t* problem,
                          const double* T0, const double* P0, const double* V0, const double* Y0, const double* t,
                          const double* y, const ckmi_reactor_ext* ext, const ckmi_rhs_psr* psr, double* f, double* J,
                          void* stream) {
-  if (!m || !cfg || n < 0) return fail(CKMI_ERR_ARG, "bad argument");
+  if (!m || !cfg || n < 0) return set_error(CKMI_ERR_ARG, "bad argument");
   if (n > 0 && (!problem || !T0 || !P0 || !V0 || !Y0 || !t || !y || !f))
-    return fail(CKMI_ERR_ARG, "problem, T0, P0, V0, Y0, t, y and f are required");
-  if (cfg->energy != 1 && cfg->energy != 2) return fail(CKMI_ERR_ARG, "energy must be 1 or 2");
-  if (cfg->nprof < 0 || cfg->nprof > 64 || cfg->nprof2 < 0 || cfg->nprof2 > 64 || cfg->nprof3 < 0 || cfg->nprof3 > 64)
-    return fail(CKMI_ERR_ARG, "nprof, nprof2, nprof3 must be in [0, 64]");
-  if (cfg->prof_kind != 0 && cfg->prof_kind != 1) return fail(CKMI_ERR_ARG, "prof_kind must be 0 (VPRO/PPRO) or 1 (TPRO)");
-  if (cfg->prof_kind == 1 && cfg->energy != 2) return fail(CKMI_ERR_ARG, "TPRO needs a given-temperature run (energy = 2)");
-  if (cfg->nprof2 > 0 && cfg->prof2_kind != 1 && cfg->prof2_kind != 2)
-    return fail(CKMI_ERR_ARG, "prof2_kind must be 1 (QPRO) or 2 (AEXT)");
-  if (cfg->nprof2 > 0 && cfg->energy != 1) return fail(CKMI_ERR_ARG, "QPRO / AEXT need an energy-equation run");
-  if (cfg->nprof3 > 0 && !(cfg->nprof2 > 0 && cfg->prof2_kind == 1))
-    return fail(CKMI_ERR_ARG, "the third profile (AEXT) needs a QPRO second profile");
-  if (!(cfg->gfac >= 0.0)) return fail(CKMI_ERR_ARG, "GFAC must be >= 0");
-  if (!(cfg->htc >= 0.0) || !(cfg->areaq >= 0.0) || !(cfg->tamb > 0.0 || cfg->htc * cfg->areaq == 0.0))
-    return fail(CKMI_ERR_ARG, "HTC, AREAQ must be >= 0 and TAMB > 0");
-  if (ext && (ext->afac_rxn != nullptr) != (ext->afac != nullptr)) return fail(CKMI_ERR_ARG, "afac_rxn and afac go together");
+    return set_error(CKMI_ERR_ARG, "problem, T0, P0, V0, Y0, t, y and f are required");
+  if (int rc = check_reactor_cfg(cfg, ext, true)) return rc;
   if (n == 0) return CKMI_OK;
   const hipStream_t st = (hipStream_t)stream;
   // the problems decide the kernel: checked on the host (one synchronous copy; a diagnostic call)
   std::vector<int32_t> hp(n);
-  HIP_CHECK(hipMemcpyAsync(hp.data(), problem, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  CKMI_HIP_CHECK(hipMemcpyAsync(hp.data(), problem, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  CKMI_HIP_CHECK(hipStreamSynchronize(st));
   int n_lo = 0, n_pf = 0, n_eng = 0, n_psr = 0;
   for (int32_t p : hp) {
-    if (p < 1 || p > 5) return fail(CKMI_ERR_ARG, "problem must be 1..5 for every state");
+    if (p < 1 || p > 5) return set_error(CKMI_ERR_ARG, "problem must be 1..5 for every state");
     n_lo += p <= 2, n_pf += p == 3, n_eng += p == 4, n_psr += p == 5;
   }
-  if (n_psr && n_psr != n) return fail(CKMI_ERR_ARG, "open reactors (problem 5) cannot share a call with closed ones");
+  if (n_psr && n_psr != n) return set_error(CKMI_ERR_ARG, "open reactors (problem 5) cannot share a call with closed ones");
   const int nvar = m->KK + 1;
   const int rpath = g_reactor_path.load();
-  if ((n_eng || n_psr) && nvar > WAVE)
-    return fail(CKMI_ERR_UNSUPPORTED, "engine and open reactors (problems 4, 5) need KK + 1 <= 64");
+  if ((n_eng || n_psr) && nvar > WAVE_NMAX)
+    return set_error(CKMI_ERR_UNSUPPORTED, "engine and open reactors (problems 4, 5) need KK + 1 <= 64");
   if (n_eng && rpath == 1)
-    return fail(CKMI_ERR_UNSUPPORTED, "engine reactors (problem 4) need the wave-per-reactor kernel");
+    return set_error(CKMI_ERR_UNSUPPORTED, "engine reactors (problem 4) need the wave-per-reactor kernel");
   if (n_eng && cfg->eng[CKMI_ENG_HTMODEL] == 1.0 && !cfg->tran)
-    return fail(CKMI_ERR_ARG, "the engine's ICHX heat transfer needs the transport fits (cfg->tran)");
+    return set_error(CKMI_ERR_ARG, "the engine's ICHX heat transfer needs the transport fits (cfg->tran)");
   if (n_psr) {
     if (!psr || (psr->mode != 1 && psr->mode != 2) || !psr->Tin || !psr->Yin || !psr->mdot)
-      return fail(CKMI_ERR_ARG, "problem 5 needs the inlet block: mode 1 or 2, Tin, Yin, mdot");
-    if (cfg->nprof != 0 || cfg->nprof2 != 0 || cfg->nprof3 != 0) return fail(CKMI_ERR_ARG, "profiles do not apply to a PSR");
+      return set_error(CKMI_ERR_ARG, "problem 5 needs the inlet block: mode 1 or 2, Tin, Yin, mdot");
+    if (cfg->nprof != 0 || cfg->nprof2 != 0 || cfg->nprof3 != 0) return set_error(CKMI_ERR_ARG, "profiles do not apply to a PSR");
   }
-  DevCfg dc;
-  dc.c = *cfg;
-  if (dc.c.gfac == 0.0) dc.c.gfac = 1.0;
-  dc.ncrit = 0;
-  dc.guard_y = std::max(1e-3, 1e3 * cfg->atol);
-  dc.guard_tlo = m->tguard_lo;
-  dc.guard_thi = m->tguard_hi;
-  dc.npe = 0;  // (no integration)
+  const DevCfg dc = make_dev_cfg(m, cfg, false);
   ProbeIO io{problem, T0, P0, V0, Y0, t, y, ext ? ext->afac_rxn : nullptr, ext ? ext->afac : nullptr,
              psr ? psr->Tin : nullptr, psr ? psr->Yin : nullptr, psr ? psr->mdot : nullptr, psr ? psr->mode : 0, f, J};
   if (n_psr) return launch_psr_probe(m, n, dc, io, st);
-  if (nvar > WAVE || rpath == 1) return launch_big_probe(m, n, dc, io, st);
-  // the template parameters ckmi_reactor_run_ex picks: problems 1 and 2 in the FP32-inverse variant (PF = false,
-  // N = 32 / 54 / 64) unless the FP64 inverse is selected, plug flow and engines in the FP64-inverse one (PF = true)
-  const bool f64 = rpath == 2 || (rpath != 3 && (cfg->rtol < 1e-9 || m->has_general));
-  const int n_hi = n_pf + n_eng;
-  int rc = CKMI_OK;
-  if (m->has_plog) {
-    if (!f64 && n_lo) rc = launch_rhs_probe<true, false, false>(m, n, dc, io, SEL_NO_PFR, 64, st);
-    if (!rc && (f64 || n_hi)) rc = launch_rhs_probe<true, true, false>(m, n, dc, io, f64 ? SEL_ALL : SEL_PFR, 64, st);
+  if (use_workgroup_kernel(nvar, rpath)) return launch_big_probe(m, n, dc, io, st);
+  // the plan of ckmi_reactor_run_ex: problems 1 and 2 in the FP32-inverse variant (PF = false) unless the FP64
+  // inverse is selected, plug flow and engines in the FP64-inverse one (PF = true); a launch with no state is left out
+  const WavePlan p = wave_plan(nvar, m->has_plog, m->has_general, cfg->rtol, rpath, false);
+  const int sel = p.f64_takes == F64_TAKES_ALL ? SEL_ALL : SEL_PFR;  // (one evaluation: nothing to take again)
+  const auto probe = [&](auto PL) {
+    int rc = CKMI_OK;
+    if (p.n32 && n_lo) rc = launch_rhs_probe<decltype(PL)::value, false, false>(m, n, dc, io, SEL_NO_PFR, p.n32, st);
+    if (!rc && (!p.n32 || n_pf + n_eng)) rc = launch_rhs_probe<decltype(PL)::value, true, false>(m, n, dc, io, sel, p.n64, st);
+    return rc;
+  };
+  return p.pl ? probe(std::true_type{}) : probe(std::false_type{});
+}
+
+int ckmi_reactor_variant(int32_t nvar, int32_t has_plog, int32_t has_general, double rtol, int32_t path,
+                         int32_t open_reactor, int32_t out[5]) {
+  if (nvar < 2 || path < 0 || path > 3 || !out) return CKMI_ERR_ARG;
+  std::fill(out, out + 5, 0);
+  if (!open_reactor && use_workgroup_kernel(nvar, path)) {
+    const BigPlan p = big_plan(nvar, has_plog != 0);
+    if (p.nb == 0) return CKMI_ERR_UNSUPPORTED;
+    out[0] = 2, out[1] = p.nb, out[3] = p.pl;
   } else {
-    const int n64 = nvar <= 54 ? 54 : 64;
-    if (!f64 && n_lo) rc = launch_rhs_probe<false, false, false>(m, n, dc, io, SEL_NO_PFR, nvar <= 32 ? 32 : n64, st);
-    if (!rc && (f64 || n_hi)) rc = launch_rhs_probe<false, true, false>(m, n, dc, io, f64 ? SEL_ALL : SEL_PFR, n64, st);
+    if (nvar > WAVE_NMAX) return CKMI_ERR_UNSUPPORTED;  // open reactors exist in the wave kernel only
+    const WavePlan p = wave_plan(nvar, has_plog != 0, has_general != 0, rtol, path, open_reactor != 0);
+    out[0] = 1, out[1] = p.n32, out[2] = p.n64, out[3] = p.pl, out[4] = p.f64_takes;
   }
-  return rc;
+  return CKMI_OK;
 }
 
 int ckmi_set_reactor_path(int32_t path) {
   if (path < 0 || path > 3)
-    return fail(CKMI_ERR_ARG, "reactor path must be 0 (automatic), 1 (workgroup), 2 (wave, FP64 inverse) or 3 (wave, "
+    return set_error(CKMI_ERR_ARG, "reactor path must be 0 (automatic), 1 (workgroup), 2 (wave, FP64 inverse) or 3 (wave, "
                               "FP32-stored inverse)");
   g_reactor_path = path;
   return CKMI_OK;

@@ -34,7 +34,6 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <map>
 #include <string>
 
 #include "ckmi_internal.hpp"
@@ -45,7 +44,6 @@ namespace {
 
 constexpr int BW = 4;           // waves per workgroup
 constexpr int NT = BW * WAVE;   // threads: state component / matrix row per thread
-constexpr int BIG_NMAX = 192;   // n = KK + 1 <= 192
 constexpr int RED_SET = 72;     // doubles per reduction set (two sets alternate): [BW][16] + [BW] for bsumn_max<16>
 constexpr int NDQ = 16;         // dq/dC slots per reaction: unit reactions 4 + 4, general ones GEN_SLOTS + GEN_SLOTS
 constexpr int XS = NT + 16;     // row stride of the MFMA form's solve partial sums [NB][XS] (bank-conflict-free)
@@ -64,12 +62,6 @@ __device__ unsigned long long* g_big_phase_buf = nullptr;
 #define BPH_T0() (void)0
 #define BPH_ADD(slot) (void)0
 #endif
-
-#define BIG_CHECK(x)                                                                                 \
-  do {                                                                                              \
-    hipError_t _e = (x);                                                                            \
-    if (_e != hipSuccess) return set_error(CKMI_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 // LDS layout of the workgroup (byte offsets; the mechanism image is at 0)
 struct BigLds {
@@ -1419,42 +1411,30 @@ BigLds big_layout(int img_bytes, int KKp, int G, int NC, int lds_max) {
 template <int NB, bool PL>
 int launch_big_nc(const ckmi_mech* m, int n, const DevCfg& dc, const ReactorIO& io, hipStream_t stream) {
   int lds_max = 0, ncu = 0, per_cu = 0;
-  BIG_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
-  BIG_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, m->device));
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, m->device));
   const BigLds L = big_layout(m->img.bytes, m->img.KKp, m->img.G, 16 * NB, lds_max);
   if (L.jcb < BW)
     return set_error(CKMI_ERR_SIZE, "mechanism image too large for the workgroup-per-reactor kernel's LDS (" +
                                         std::to_string(m->img.bytes) + " B image)");
-  static thread_local std::map<std::pair<int, const void*>, int> lds_set;
-  const void* fn = (const void*)big_reactor_kernel<NB, PL>;
-  if (lds_set[{m->device, fn}] < L.bytes) {
-    BIG_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, L.bytes));
-    lds_set[{m->device, fn}] = L.bytes;
-  }
-  BIG_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, big_reactor_kernel<NB, PL>, NT, L.bytes));
+  if (int rc = raise_lds_limit(m->device, (const void*)big_reactor_kernel<NB, PL>, L.bytes)) return rc;
+  CKMI_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, big_reactor_kernel<NB, PL>, NT, L.bytes));
   if (per_cu < 1) return set_error(CKMI_ERR_SIZE, "workgroup-per-reactor kernel does not fit on a CU");
   const int grid = std::max(1, std::min(ncu * per_cu, n));
-  const size_t jbytes = ((size_t)grid * jslot_floats(NB) * sizeof(float) + 255) & ~(size_t)255;
-  const size_t dbytes = ((size_t)grid * NDQ * m->img.IIp * sizeof(double) + 255) & ~(size_t)255;
-  const size_t cbytes = (sizeof(DevCfg) + 255) & ~(size_t)255;
-  void* ws = nullptr;
-  BIG_CHECK(hipMallocAsync(&ws, jbytes + dbytes + cbytes + 256, stream));
-  char* base = (char*)ws;
-  DevCfg* dcfg = (DevCfg*)(base + jbytes + dbytes);
-  int* queue = (int*)(base + jbytes + dbytes + cbytes);
-  auto* hc = new DevCfg(dc);
-  hipError_t e = hipMemcpyAsync(dcfg, hc, sizeof(DevCfg), hipMemcpyHostToDevice, stream);
-  if (e != hipSuccess) {
-    delete hc;
-    (void)hipFreeAsync(ws, stream);
-    return set_error(CKMI_ERR_HIP, std::string("cfg copy: ") + hipGetErrorString(e));
-  }
-  BIG_CHECK(hipLaunchHostFunc(stream, [](void* p) { delete static_cast<DevCfg*>(p); }, hc));
-  BIG_CHECK(hipMemsetAsync(queue, 0, sizeof(int), stream));
+  const size_t jbytes = StreamWorkspace::aligned((size_t)grid * jslot_floats(NB) * sizeof(float));
+  const size_t dbytes = StreamWorkspace::aligned((size_t)grid * NDQ * m->img.IIp * sizeof(double));
+  const size_t cbytes = StreamWorkspace::aligned(sizeof(DevCfg));
+  StreamWorkspace ws(stream);
+  if (int rc = ws.alloc(jbytes + dbytes + cbytes + 256)) return rc;
+  float* jws = ws.take<float>(jbytes);
+  double* dws = ws.take<double>(dbytes);
+  DevCfg* dcfg = ws.take<DevCfg>(cbytes);
+  int* queue = ws.take<int>(256);
+  if (int rc = stage_cfg(dc, dcfg, stream)) return rc;
+  CKMI_HIP_CHECK(hipMemsetAsync(queue, 0, sizeof(int), stream));
   hipLaunchKernelGGL((big_reactor_kernel<NB, PL>), dim3(grid), dim3(NT), L.bytes, stream, m->img, L, dcfg, n, queue,
-                     (float*)base, (double*)(base + jbytes), io);
-  BIG_CHECK(hipGetLastError());
-  BIG_CHECK(hipFreeAsync(ws, stream));
+                     jws, dws, io);
+  CKMI_HIP_CHECK(hipGetLastError());
   return CKMI_OK;
 }
 
@@ -1546,82 +1526,52 @@ __global__ __launch_bounds__(NT, 1) void big_rhs_probe_kernel(MechImage img, Big
 template <bool PL>
 int launch_big_probe_nb(const ckmi_mech* m, int n, int NB, const DevCfg& dc, const ProbeIO& io, hipStream_t stream) {
   int lds_max = 0;
-  BIG_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
   const BigLds L = big_layout(m->img.bytes, m->img.KKp, m->img.G, 16 * NB, lds_max);
   if (L.jcb < BW || L.bytes > lds_max)  // the capacity check of launch_big_nc
     return set_error(CKMI_ERR_SIZE, "mechanism image too large for the workgroup-per-reactor kernel's LDS (" +
                                         std::to_string(m->img.bytes) + " B image)");
-  const void* fn = (const void*)big_rhs_probe_kernel<PL>;
-  BIG_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, L.bytes));
+  if (int rc = raise_lds_limit(m->device, (const void*)big_rhs_probe_kernel<PL>, L.bytes)) return rc;
   const int grid = std::min(n, PROBE_GRID_MAX);
-  const size_t jbytes = ((size_t)grid * jslot_floats(NB) * sizeof(float) + 255) & ~(size_t)255;
-  const size_t dbytes = ((size_t)grid * NDQ * m->img.IIp * sizeof(double) + 255) & ~(size_t)255;
-  const size_t cbytes = (sizeof(DevCfg) + 255) & ~(size_t)255;
-  void* ws = nullptr;
-  BIG_CHECK(hipMallocAsync(&ws, jbytes + dbytes + cbytes, stream));
-  char* base = (char*)ws;
-  DevCfg* dcfg = (DevCfg*)(base + jbytes + dbytes);
-  auto* hc = new DevCfg(dc);
-  hipError_t e = hipMemcpyAsync(dcfg, hc, sizeof(DevCfg), hipMemcpyHostToDevice, stream);
-  if (e != hipSuccess) {
-    delete hc;
-    (void)hipFreeAsync(ws, stream);
-    return set_error(CKMI_ERR_HIP, std::string("cfg copy: ") + hipGetErrorString(e));
-  }
-  BIG_CHECK(hipLaunchHostFunc(stream, [](void* p) { delete static_cast<DevCfg*>(p); }, hc));
-  hipLaunchKernelGGL((big_rhs_probe_kernel<PL>), dim3(grid), dim3(NT), L.bytes, stream, m->img, L, dcfg, n, NB,
-                     (float*)base, (double*)(base + jbytes), io);
-  BIG_CHECK(hipGetLastError());
-  BIG_CHECK(hipFreeAsync(ws, stream));
+  const size_t jbytes = StreamWorkspace::aligned((size_t)grid * jslot_floats(NB) * sizeof(float));
+  const size_t dbytes = StreamWorkspace::aligned((size_t)grid * NDQ * m->img.IIp * sizeof(double));
+  const size_t cbytes = StreamWorkspace::aligned(sizeof(DevCfg));
+  StreamWorkspace ws(stream);
+  if (int rc = ws.alloc(jbytes + dbytes + cbytes)) return rc;
+  float* jws = ws.take<float>(jbytes);
+  double* dws = ws.take<double>(dbytes);
+  DevCfg* dcfg = ws.take<DevCfg>(cbytes);
+  if (int rc = stage_cfg(dc, dcfg, stream)) return rc;
+  hipLaunchKernelGGL((big_rhs_probe_kernel<PL>), dim3(grid), dim3(NT), L.bytes, stream, m->img, L, dcfg, n, NB, jws, dws,
+                     io);
+  CKMI_HIP_CHECK(hipGetLastError());
   return CKMI_OK;
 }
 
 }  // namespace
 
-// the NB and PL launch_big_reactors picks for the mechanism
-int launch_big_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream) {
-  const int nvar = m->KK + 1;
-  if (nvar > BIG_NMAX)
+// the plan of the mechanism (ckmi_dispatch.hpp); the refusal above BIG_NMAX
+static int big_plan_of(const ckmi_mech* m, BigPlan* p) {
+  *p = big_plan(m->KK + 1, m->has_plog);
+  if (p->nb == 0)
     return set_error(CKMI_ERR_UNSUPPORTED, "batch reactors with more than " + std::to_string(BIG_NMAX - 1) +
                                                " species are not supported (the ROP/thermo kernels are)");
-  if (m->has_plog) return launch_big_probe_nb<true>(m, n, nvar <= 128 ? 8 : (nvar <= 176 ? 11 : 12), dc, io, stream);
-  return launch_big_probe_nb<false>(m, n, std::min(12, std::max(4, (nvar + 15) / 16)), dc, io, stream);
+  return CKMI_OK;
+}
+
+// the probe takes NB at run time: the NB and PL launch_big_reactors runs the mechanism in
+int launch_big_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream) {
+  BigPlan p;
+  if (int rc = big_plan_of(m, &p)) return rc;
+  return p.pl ? launch_big_probe_nb<true>(m, n, p.nb, dc, io, stream) : launch_big_probe_nb<false>(m, n, p.nb, dc, io, stream);
 }
 
 int launch_big_reactors(const ckmi_mech* m, int n, const DevCfg& dc, const ReactorIO& io, hipStream_t stream) {
-  const int nvar = m->KK + 1;
-  if (nvar > BIG_NMAX)
-    return set_error(CKMI_ERR_UNSUPPORTED, "batch reactors with more than " + std::to_string(BIG_NMAX - 1) +
-                                               " species are not supported (the ROP/thermo kernels are)");
-  if (m->has_plog) {
-    // PLOG, chemically activated and general (FORD / RORD / fractional) reactions: the extended
-    // variant, compiled for three matrix sizes (a mechanism runs in the smallest that holds it)
-#ifdef CKMI_BIG_ONLY_NB
-    return set_error(CKMI_ERR_UNSUPPORTED, "diagnostic build: no extended variants");
-#else
-    if (nvar <= 128) return launch_big_nc<8, true>(m, n, dc, io, stream);
-    if (nvar <= 176) return launch_big_nc<11, true>(m, n, dc, io, stream);
-    return launch_big_nc<12, true>(m, n, dc, io, stream);
-#endif
-  }
-  switch ((nvar + 15) / 16) {  // NB: register blocks per dimension (NC = 16 NB >= n)
-    case 1:
-    case 2:
-    case 3:
-#ifdef CKMI_BIG_ONLY_NB  // diagnostics: compile one matrix size only (register-usage checks)
-    default: return launch_big_nc<CKMI_BIG_ONLY_NB, false>(m, n, dc, io, stream);
-#else
-    case 4: return launch_big_nc<4, false>(m, n, dc, io, stream);
-    case 5: return launch_big_nc<5, false>(m, n, dc, io, stream);
-    case 6: return launch_big_nc<6, false>(m, n, dc, io, stream);
-    case 7: return launch_big_nc<7, false>(m, n, dc, io, stream);
-    case 8: return launch_big_nc<8, false>(m, n, dc, io, stream);
-    case 9: return launch_big_nc<9, false>(m, n, dc, io, stream);
-    case 10: return launch_big_nc<10, false>(m, n, dc, io, stream);
-    case 11: return launch_big_nc<11, false>(m, n, dc, io, stream);
-    default: return launch_big_nc<12, false>(m, n, dc, io, stream);
-#endif
-  }
+  BigPlan p;
+  if (int rc = big_plan_of(m, &p)) return rc;
+  return visit_big_variant(p, [&](auto NB, auto PL) {
+    return launch_big_nc<decltype(NB)::value, decltype(PL)::value>(m, n, dc, io, stream);
+  });
 }
 
 }  // namespace ckmi
@@ -1638,7 +1588,7 @@ extern "C" int ckmi_debug_big_phase_buffer(void* buf) {
 // (KKp padded species, G third-body groups) on a CU with lds_max bytes of LDS; -1 if none fits.  Host-only.
 extern "C" int ckmi_big_max_image_bytes(int nvar, int KKp, int G, int lds_max) {
   if (nvar < 1 || nvar > ckmi::BIG_NMAX) return -1;
-  const int NC = 16 * ((nvar + 15) / 16 < 4 ? 4 : (nvar + 15) / 16);
+  const int NC = 16 * ckmi::big_plan(nvar, false).nb;
   int best = -1;
   for (int lo = 0, hi = lds_max; lo <= hi;) {
     const int mid = ((lo + hi) / 2) & ~15;

@@ -16,13 +16,6 @@
 
 using namespace ckmi;
 
-#define HIP_CHECK(x)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) return ckmi::set_error(CKMI_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-static int fail(int code, const std::string& msg) { return ckmi::set_error(code, msg); }
-
 namespace {
 
 constexpr int EQ_BLOCK = 256;
@@ -469,7 +462,7 @@ int equil_table(const ckmi_mech* cm) {
   ckmi_mech* m = const_cast<ckmi_mech*>(cm);
   const MechImage& I = m->img;
   std::vector<char> blob((size_t)I.bytes);
-  HIP_CHECK(hipMemcpy(blob.data(), I.blob, blob.size(), hipMemcpyDeviceToHost));
+  CKMI_HIP_CHECK(hipMemcpy(blob.data(), I.blob, blob.size(), hipMemcpyDeviceToHost));
   const double* th = (const double*)(blob.data() + I.o_th);
   const double* wt = (const double*)(blob.data() + I.o_wt);
   const uint64_t* el = (const uint64_t*)(blob.data() + I.o_e2t + 8 * E2T_N);
@@ -486,9 +479,9 @@ int equil_table(const ckmi_mech* cm) {
     memcpy(&row[EQ_MASK], &mask, 8);
   }
   void* p = nullptr;
-  HIP_CHECK(hipMalloc(&p, tab.size() * sizeof(double)));
+  CKMI_HIP_CHECK(hipMalloc(&p, tab.size() * sizeof(double)));
   m->allocs.push_back(p);
-  HIP_CHECK(hipMemcpy(p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+  CKMI_HIP_CHECK(hipMemcpy(p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
   m->eq_mm = m->npe;
   m->eq_tab = (const double*)p;
   return CKMI_OK;
@@ -498,19 +491,18 @@ template <int MM>
 int launch_equil(const ckmi_mech* m, EqArgs a, hipStream_t st) {
   const size_t lds = (size_t)a.KK * EQ_ROW * sizeof(double);
   int ncu = 0, per_cu = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, m->device));
-  HIP_CHECK(hipFuncSetAttribute((const void*)equil_kernel<MM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, equil_kernel<MM>, EQ_BLOCK, lds));
-  if (per_cu < 1) return fail(CKMI_ERR_SIZE, "equilibrium kernel does not fit on a CU");
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, m->device));
+  if (int rc = raise_lds_limit(m->device, (const void*)equil_kernel<MM>, lds)) return rc;
+  CKMI_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, equil_kernel<MM>, EQ_BLOCK, lds));
+  if (per_cu < 1) return set_error(CKMI_ERR_SIZE, "equilibrium kernel does not fit on a CU");
   const int tiles = (a.n + EQ_BLOCK - 1) / EQ_BLOCK;
   const int grid = std::max(1, std::min(ncu * per_cu, tiles));
-  void* ws = nullptr;
-  HIP_CHECK(hipMallocAsync(&ws, 3 * (size_t)a.KK * grid * EQ_BLOCK * sizeof(double), st));
-  a.ws = (double*)ws;
+  const size_t wbytes = 3 * (size_t)a.KK * grid * EQ_BLOCK * sizeof(double);
+  StreamWorkspace ws(st);
+  if (int rc = ws.alloc(wbytes)) return rc;
+  a.ws = ws.take<double>(wbytes);
   hipLaunchKernelGGL((equil_kernel<MM>), dim3(grid), dim3(EQ_BLOCK), lds, st, a);
-  const hipError_t e = hipGetLastError();
-  HIP_CHECK(hipFreeAsync(ws, st));
-  HIP_CHECK(e);
+  CKMI_HIP_CHECK(hipGetLastError());
   return CKMI_OK;
 }
 
@@ -521,18 +513,18 @@ extern "C" {
 int ckmi_equil_run(const ckmi_mech* m, const ckmi_equil_cfg* cfg, int32_t n, const int32_t* option, const double* T,
                    const double* P, const double* Y, double* Teq, double* Peq, double* Yeq, double* sound,
                    double* detspeed, int32_t* stats, void* stream) {
-  if (!m || !cfg || n < 0) return fail(CKMI_ERR_ARG, "bad argument");
+  if (!m || !cfg || n < 0) return set_error(CKMI_ERR_ARG, "bad argument");
   if (!(cfg->tol >= 0.0) || cfg->max_iter < 0 || cfg->cj_iter < 0)
-    return fail(CKMI_ERR_ARG, "tol, max_iter and cj_iter must be >= 0 (0: the default)");
+    return set_error(CKMI_ERR_ARG, "tol, max_iter and cj_iter must be >= 0 (0: the default)");
   const double vlo = cfg->cj_vlo == 0.0 ? 0.30 : cfg->cj_vlo, vhi = cfg->cj_vhi == 0.0 ? 0.97 : cfg->cj_vhi;
   const double v0 = cfg->cj_start == 0.0 ? 0.60 : cfg->cj_start;
   if (!(vlo > 0.0 && vlo < v0 && v0 < vhi && vhi < 1.0) || !(cfg->cj_tol >= 0.0))
-    return fail(CKMI_ERR_ARG, "the CJ bracket needs 0 < cj_vlo < cj_start < cj_vhi < 1 and cj_tol >= 0");
+    return set_error(CKMI_ERR_ARG, "the CJ bracket needs 0 < cj_vlo < cj_start < cj_vhi < 1 and cj_tol >= 0");
   if (m->npe < 1)
-    return fail(CKMI_ERR_UNSUPPORTED, "the equilibrium solver needs the element counts of a mechanism with at most " +
+    return set_error(CKMI_ERR_UNSUPPORTED, "the equilibrium solver needs the element counts of a mechanism with at most " +
                                           std::to_string(CKMI_PROJ_MMAX) + " elements");
   if (n > 0 && (!option || !T || !P || !Y || !Teq || !Peq || !Yeq || !sound || !detspeed || !stats))
-    return fail(CKMI_ERR_ARG, "every input and output array is required");
+    return set_error(CKMI_ERR_ARG, "every input and output array is required");
   if (n == 0) return CKMI_OK;
   if (int rc = equil_table(m)) return rc;
   EqArgs a{};
@@ -566,7 +558,7 @@ int ckmi_equil_run(const ckmi_mech* m, const ckmi_equil_cfg* cfg, int32_t n, con
     case 6: return launch_equil<6>(m, a, st);
     case 7: return launch_equil<7>(m, a, st);
     case 8: return launch_equil<8>(m, a, st);
-    default: return fail(CKMI_ERR_UNSUPPORTED, "more than 8 elements");
+    default: return set_error(CKMI_ERR_UNSUPPORTED, "more than 8 elements");
   }
 }
 

@@ -9,6 +9,7 @@
 
 #include "../../include/ckmi.h"
 #include "ckmi_device.hpp"
+#include "ckmi_dispatch.hpp"
 #include "ckmi_image.hpp"
 
 namespace ckmi {
@@ -85,13 +86,64 @@ struct ckmi_mech {
 namespace ckmi {
 struct DevCfg;
 struct ReactorIO;
-// record the message for ckmi_last_error() and return code
+struct ProbeIO;
+// record the message for ckmi_last_error() and return code: the one way to fail (ckmi.hip)
 int set_error(int code, const std::string& msg);
+
+#define CKMI_HIP_CHECK(x)                                                                                        \
+  do {                                                                                                           \
+    hipError_t e_ = (x);                                                                                         \
+    if (e_ != hipSuccess) return ckmi::set_error(CKMI_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// ---------------------------------------------------------------- the launch layer (ckmi.hip)
+// The stream-ordered workspace of one launch or call: one hipMallocAsync, released behind the work on every
+// way out, handed out front to back in 256-byte-aligned pieces.
+class StreamWorkspace {
+ public:
+  explicit StreamWorkspace(hipStream_t stream) : st_(stream) {}
+  ~StreamWorkspace() {
+    if (base_) (void)hipFreeAsync(base_, st_);
+  }
+  StreamWorkspace(const StreamWorkspace&) = delete;
+  StreamWorkspace& operator=(const StreamWorkspace&) = delete;
+  static constexpr size_t aligned(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+  int alloc(size_t bytes) {
+    CKMI_HIP_CHECK(hipMallocAsync((void**)&base_, bytes, st_));
+    return CKMI_OK;
+  }
+  // the next piece; bytes is rounded up to the alignment
+  template <class T>
+  T* take(size_t bytes) {
+    T* p = (T*)(base_ + off_);
+    off_ += aligned(bytes);
+    return p;
+  }
+
+ private:
+  hipStream_t st_;
+  char* base_ = nullptr;
+  size_t off_ = 0;
+};
+// Per-launch copy of the run configuration: it lives in the launch's stream-ordered workspace, so launches with
+// different configurations on one mechanism handle (other streams, other host threads) never share it.  The
+// host staging copy is released by a host function enqueued behind the copy, i.e. only once the stream has
+// consumed it.
+int stage_cfg(const DevCfg& dc, DevCfg* dst, hipStream_t stream);
+// raise fn's dynamic-LDS limit on device to bytes: above the 64 KiB every kernel has, and only ever upwards
+int raise_lds_limit(int device, const void* fn, size_t bytes);
+// The device configuration of a call: GFAC 0 -> 1 and the runaway guard; integrate (a closed-reactor run) adds
+// the profile breakpoints and the element projection, which the probes, the heat rates and the open reactor
+// (it relaxes to the inlet's element content, not the estimate's) leave off.
+DevCfg make_dev_cfg(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, bool integrate);
+// what ckmi_reactor_run_ex, ckmi_psr_run and ckmi_reactor_rhs_jac all require of a configuration; profiles:
+// the entry takes profiles (an open reactor refuses them itself and never reads their kinds)
+int check_reactor_cfg(const ckmi_reactor_cfg* cfg, const ckmi_reactor_ext* ext, bool profiles);
+
 // one workgroup per reactor: 64 <= KK + 1 <= 192 (ckmi_big.hip)
 int launch_big_reactors(const ckmi_mech* m, int n, const DevCfg& dc, const ReactorIO& io, hipStream_t stream);
 // RHS / Jacobian probes of ckmi_reactor_rhs_jac: the workgroup kernel's (ckmi_big.hip) and the open-reactor
 // instantiation of the wave kernel's (ckmi_psr.hip)
-struct ProbeIO;
 int launch_big_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream);
 int launch_psr_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream);
 }  // namespace ckmi

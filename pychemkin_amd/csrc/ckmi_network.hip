@@ -10,13 +10,6 @@
 
 using namespace ckmi;
 
-#define HIP_CHECK(x)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (x);                                                                                      \
-    if (e_ != hipSuccess) return ckmi::set_error(CKMI_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-static int fail(int code, const std::string& msg) { return ckmi::set_error(code, msg); }
-
 namespace {
 constexpr int RMAX = CKMI_NET_RMAX;
 constexpr int NET_BLOCK = 256;  // 4 waves: one wave per network in the mixing, scatter and tear kernels
@@ -298,22 +291,22 @@ __global__ __launch_bounds__(NET_BLOCK) void net_tear_kernel(NetIO io, int n_act
 
 // the call's stream-ordered workspace and its pinned count, released on every way out
 struct NetScratch {
-  void* ws = nullptr;
+  hipStream_t st;
+  StreamWorkspace ws;
   int* hcount = nullptr;
-  hipStream_t st = nullptr;
+  explicit NetScratch(hipStream_t stream) : st(stream), ws(stream) {}
   ~NetScratch() {
-    if (ws) (void)hipFreeAsync(ws, st);
     if (hcount) (void)hipHostFree(hcount);
   }
 };
 
 int read_count(const NetIO& io, NetScratch& sc, int* n_act) {
   hipLaunchKernelGGL(net_compact_kernel, dim3(1), dim3(WAVE), 0, sc.st, io);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(sc.hcount, io.count, sizeof(int), hipMemcpyDeviceToHost, sc.st));
-  HIP_CHECK(hipStreamSynchronize(sc.st));
+  CKMI_HIP_CHECK(hipGetLastError());
+  CKMI_HIP_CHECK(hipMemcpyAsync(sc.hcount, io.count, sizeof(int), hipMemcpyDeviceToHost, sc.st));
+  CKMI_HIP_CHECK(hipStreamSynchronize(sc.st));
   *n_act = *sc.hcount;
-  if (*n_act < 0 || *n_act > io.n_net) return fail(CKMI_ERR_HIP, "internal: active network count out of range");
+  if (*n_act < 0 || *n_act > io.n_net) return set_error(CKMI_ERR_HIP, "internal: active network count out of range");
   return CKMI_OK;
 }
 }  // namespace
@@ -327,19 +320,19 @@ int ckmi_psr_network_run(const ckmi_mech* m, int32_t n_net, int32_t R, int32_t E
                          const int32_t* tear, double* Tss, double* Yss, double* mdot, double* rho, double* tau_res,
                          double* vol, double* resid, int32_t* stats, int32_t* net_stats, double* tear_resid,
                          void* stream) {
-  if (!m || !cfg || !psr || !net || !guess_mode || n_net < 0 || R < 1 || E < 1) return fail(CKMI_ERR_ARG, "bad argument");
+  if (!m || !cfg || !psr || !net || !guess_mode || n_net < 0 || R < 1 || E < 1) return set_error(CKMI_ERR_ARG, "bad argument");
   if (R > RMAX)
-    return fail(CKMI_ERR_UNSUPPORTED, "a network has at most " + std::to_string(RMAX) + " reactors, not " + std::to_string(R));
+    return set_error(CKMI_ERR_UNSUPPORTED, "a network has at most " + std::to_string(RMAX) + " reactors, not " + std::to_string(R));
   if (m->KK + 1 > WAVE)
-    return fail(CKMI_ERR_UNSUPPORTED, "PSR networks need KK + 1 <= 64 (the wave-per-reactor kernel); this mechanism has " +
+    return set_error(CKMI_ERR_UNSUPPORTED, "PSR networks need KK + 1 <= 64 (the wave-per-reactor kernel); this mechanism has " +
                                           std::to_string(m->KK) + " species");
   const int max_sweeps = net->max_sweeps == 0 ? 200 : net->max_sweeps;
   const double rtol = net->tear_rtol == 0.0 ? 1e-6 : net->tear_rtol, atol = net->tear_atol == 0.0 ? 1e-8 : net->tear_atol;
   const double relax = net->relax == 0.0 ? 1.0 : net->relax;
   if (max_sweeps < 1 || !(rtol > 0.0) || !(atol >= 0.0) || !(relax > 0.0))
-    return fail(CKMI_ERR_ARG, "max_sweeps must be >= 1, tear_rtol > 0, tear_atol >= 0 and relax > 0");
+    return set_error(CKMI_ERR_ARG, "max_sweeps must be >= 1, tear_rtol > 0, tear_atol >= 0 and relax > 0");
   for (int i = 0; i < R; ++i) {
-    if (guess_mode[i] != 0 && guess_mode[i] != 1) return fail(CKMI_ERR_ARG, "guess_mode must be 0 or 1");
+    if (guess_mode[i] != 0 && guess_mode[i] != 1) return set_error(CKMI_ERR_ARG, "guess_mode must be 0 or 1");
     // an empty launch checks the position's configuration before anything runs
     const int rc = ckmi_psr_run(m, &cfg[i], &psr[i], 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
@@ -347,23 +340,22 @@ int ckmi_psr_network_run(const ckmi_mech* m, int32_t n_net, int32_t R, int32_t E
   }
   if (n_net > 0 && (!P || !split || !ext_mdot || !ext_T || !ext_Y || !tau_or_vol || !Tguess || !Yguess || !tear || !Tss ||
                     !Yss || !mdot || !rho || !tau_res || !vol || !resid || !stats || !net_stats || !tear_resid))
-    return fail(CKMI_ERR_ARG, "every input and output array is required");
+    return set_error(CKMI_ERR_ARG, "every input and output array is required");
   if (n_net == 0) return CKMI_OK;
   const int KK = m->KK;
-  NetScratch sc;
-  sc.st = (hipStream_t)stream;
+  NetScratch sc((hipStream_t)stream);
   const size_t n = (size_t)n_net;
   const size_t nd = n * ((size_t)R * (KK + 1) + 10 + 3 * (size_t)KK);  // doubles
   const size_t ni = n * (2 + CKMI_NSTAT) + 1;                           // ints
-  HIP_CHECK(hipMallocAsync(&sc.ws, nd * sizeof(double) + ni * sizeof(int), sc.st));
-  HIP_CHECK(hipHostMalloc((void**)&sc.hcount, sizeof(int), hipHostMallocDefault));
+  if (int rc = sc.ws.alloc(nd * sizeof(double) + ni * sizeof(int))) return rc;
+  CKMI_HIP_CHECK(hipHostMalloc((void**)&sc.hcount, sizeof(int), hipHostMallocDefault));
   NetIO io{};
   io.n_net = n_net, io.R = R, io.E = E, io.KK = KK;
   io.P = P, io.split = split, io.ext_mdot = ext_mdot, io.ext_T = ext_T, io.ext_Y = ext_Y, io.tau_or_vol = tau_or_vol;
   io.Tguess = Tguess, io.Yguess = Yguess, io.tear = tear;
   io.Tss = Tss, io.Yss = Yss, io.mdot = mdot, io.rho = rho, io.tau_res = tau_res, io.vol = vol, io.resid = resid;
   io.stats = stats, io.net_stats = net_stats, io.tear_resid = tear_resid;
-  double* d = (double*)sc.ws;
+  double* d = sc.ws.take<double>(nd * sizeof(double) + ni * sizeof(int));  // one piece, laid out below
   auto take = [&](size_t cnt) {
     double* p = d;
     d += cnt;
@@ -377,7 +369,7 @@ int ckmi_psr_network_run(const ckmi_mech* m, int32_t n_net, int32_t R, int32_t E
   io.live = q, io.act = q + n, io.cstats = q + 2 * n, io.count = q + (2 + CKMI_NSTAT) * n;
 
   hipLaunchKernelGGL(net_flow_kernel, dim3((n_net + NET_BLOCK - 1) / NET_BLOCK), dim3(NET_BLOCK), 0, sc.st, io);
-  HIP_CHECK(hipGetLastError());
+  CKMI_HIP_CHECK(hipGetLastError());
   int n_act = 0;
   int rc = read_count(io, sc, &n_act);
   if (rc) return rc;
@@ -386,15 +378,15 @@ int ckmi_psr_network_run(const ckmi_mech* m, int32_t n_net, int32_t R, int32_t E
     for (int pos = 0; pos < R; ++pos) {
       hipLaunchKernelGGL(net_mix_kernel, grid, dim3(NET_BLOCK), 0, sc.st, io, m->d, n_act, pos, sweep, (int)guess_mode[pos],
                          (int)psr[pos].mode);
-      HIP_CHECK(hipGetLastError());
+      CKMI_HIP_CHECK(hipGetLastError());
       rc = ckmi_psr_run(m, &cfg[pos], &psr[pos], n_act, io.cP, io.cTin, io.cYin, io.cmdot, io.ctv, io.cTg, io.cYg, io.cTss,
                         io.cYss, io.crho, io.ctau, io.cvol, io.cresid, io.cstats, stream);
       if (rc) return rc;
       hipLaunchKernelGGL(net_scatter_kernel, grid, dim3(NET_BLOCK), 0, sc.st, io, n_act, pos, sweep);
-      HIP_CHECK(hipGetLastError());
+      CKMI_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(net_tear_kernel, grid, dim3(NET_BLOCK), 0, sc.st, io, n_act, sweep, max_sweeps, rtol, atol, relax);
-    HIP_CHECK(hipGetLastError());
+    CKMI_HIP_CHECK(hipGetLastError());
     rc = read_count(io, sc, &n_act);
     if (rc) return rc;
   }

@@ -4,14 +4,11 @@
 
 using namespace ckmi;
 
-#define HIP_CHECK(x) CKMI_RK_HIP_CHECK(x)
-static int fail(int code, const std::string& msg) { return ckmi::set_error(code, msg); }
-
-// ckmi_reactor_rhs_jac on open reactors: the PSR = true instantiation ckmi_psr_run would pick
+// ckmi_reactor_rhs_jac on open reactors: the PSR = true instantiation ckmi_psr_run picks
 int ckmi::launch_psr_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream) {
-  const int nvar = m->KK + 1;
-  if (m->has_plog) return launch_rhs_probe<true, true, true>(m, n, dc, io, SEL_ALL, 64, stream);
-  return launch_rhs_probe<false, true, true>(m, n, dc, io, SEL_ALL, nvar <= 54 ? 54 : 64, stream);
+  const WavePlan p = wave_plan(m->KK + 1, m->has_plog, m->has_general, dc.c.rtol, 0, true);
+  return p.pl ? launch_rhs_probe<true, true, true>(m, n, dc, io, SEL_ALL, p.n64, stream)
+              : launch_rhs_probe<false, true, true>(m, n, dc, io, SEL_ALL, p.n64, stream);
 }
 
 extern "C" {
@@ -20,33 +17,23 @@ int ckmi_psr_run(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, const ckmi_psr
                  const double* Tin, const double* Yin, const double* mdot, const double* tau_or_vol,
                  const double* Tguess, const double* Yguess, double* Tss, double* Yss, double* rho, double* tau_res,
                  double* vol, double* resid, int32_t* stats, void* stream) {
-  if (!m || !cfg || !psr || n < 0) return fail(CKMI_ERR_ARG, "bad argument");
-  if (psr->mode != 1 && psr->mode != 2) return fail(CKMI_ERR_ARG, "psr mode must be 1 (residence time) or 2 (volume)");
-  if (!(psr->ss_rtol > 0.0) || !(psr->ss_atol >= 0.0)) return fail(CKMI_ERR_ARG, "ss_rtol must be > 0 and ss_atol >= 0");
+  if (!m || !cfg || !psr || n < 0) return set_error(CKMI_ERR_ARG, "bad argument");
+  if (psr->mode != 1 && psr->mode != 2) return set_error(CKMI_ERR_ARG, "psr mode must be 1 (residence time) or 2 (volume)");
+  if (!(psr->ss_rtol > 0.0) || !(psr->ss_atol >= 0.0)) return set_error(CKMI_ERR_ARG, "ss_rtol must be > 0 and ss_atol >= 0");
   if (!(cfg->t_end >= 0.0) || !(cfg->rtol > 0.0) || !(cfg->atol > 0.0))
-    return fail(CKMI_ERR_ARG, "t_end must be >= 0 (0: 1000 residence times), rtol and atol > 0");
-  if (cfg->energy != 1 && cfg->energy != 2) return fail(CKMI_ERR_ARG, "energy must be 1 or 2");
-  if (cfg->ign_mode != 0 || cfg->ign_stop) return fail(CKMI_ERR_ARG, "ignition detection does not apply to a PSR");
-  if (cfg->nprof != 0 || cfg->nprof2 != 0 || cfg->nprof3 != 0) return fail(CKMI_ERR_ARG, "profiles do not apply to a PSR");
-  if (cfg->asteps != 0 || cfg->avar >= 0) return fail(CKMI_ERR_ARG, "adaptive saving does not apply to a PSR");
-  if (!(cfg->gfac >= 0.0)) return fail(CKMI_ERR_ARG, "GFAC must be >= 0");
-  if (!(cfg->htc >= 0.0) || !(cfg->areaq >= 0.0) || !(cfg->tamb > 0.0 || cfg->htc * cfg->areaq == 0.0))
-    return fail(CKMI_ERR_ARG, "HTC, AREAQ must be >= 0 and TAMB > 0");
-  if (m->KK + 1 > WAVE)
-    return fail(CKMI_ERR_UNSUPPORTED, "PSRs need KK + 1 <= 64 (the wave-per-reactor kernel); this mechanism has " +
+    return set_error(CKMI_ERR_ARG, "t_end must be >= 0 (0: 1000 residence times), rtol and atol > 0");
+  if (cfg->ign_mode != 0 || cfg->ign_stop) return set_error(CKMI_ERR_ARG, "ignition detection does not apply to a PSR");
+  if (cfg->nprof != 0 || cfg->nprof2 != 0 || cfg->nprof3 != 0) return set_error(CKMI_ERR_ARG, "profiles do not apply to a PSR");
+  if (cfg->asteps != 0 || cfg->avar >= 0) return set_error(CKMI_ERR_ARG, "adaptive saving does not apply to a PSR");
+  if (int rc = check_reactor_cfg(cfg, nullptr, false)) return rc;
+  if (m->KK + 1 > WAVE_NMAX)
+    return set_error(CKMI_ERR_UNSUPPORTED, "PSRs need KK + 1 <= 64 (the wave-per-reactor kernel); this mechanism has " +
                                           std::to_string(m->KK) + " species");
   if (n > 0 && (!P || !Tin || !Yin || !mdot || !tau_or_vol || !Tguess || !Yguess || !Tss || !Yss || !rho || !tau_res ||
                 !vol || !resid || !stats))
-    return fail(CKMI_ERR_ARG, "every input and output array is required");
+    return set_error(CKMI_ERR_ARG, "every input and output array is required");
   if (n == 0) return CKMI_OK;
-  DevCfg dc;
-  dc.c = *cfg;
-  if (dc.c.gfac == 0.0) dc.c.gfac = 1.0;
-  dc.ncrit = 0;
-  dc.guard_y = std::max(1e-3, 1e3 * cfg->atol);
-  dc.guard_tlo = m->tguard_lo;
-  dc.guard_thi = m->tguard_hi;
-  dc.npe = 0;  // an open reactor relaxes to the inlet's element content, not the estimate's
+  const DevCfg dc = make_dev_cfg(m, cfg, false);  // (no element projection: see make_dev_cfg)
   PsrIO io{};
   io.T0 = Tguess;
   io.P0 = P;
@@ -67,14 +54,13 @@ int ckmi_psr_run(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, const ckmi_psr
   io.ss_rtol = psr->ss_rtol;
   io.ss_atol = psr->ss_atol;
   const hipStream_t st = (hipStream_t)stream;
-  const int nvar = m->KK + 1;
-  int rc;
-  // the FP64-inverse variants, whatever the tolerances: N = 54, N = 64 and the PLOG variant
-  if (m->has_plog) rc = launch_reactors<64, true, true, true>(m, n, dc, io, st);
-  else if (nvar <= 54) rc = launch_reactors<54, false, true, true>(m, n, dc, io, st);
-  else rc = launch_reactors<64, false, true, true>(m, n, dc, io, st);
+  // the FP64-inverse variants, whatever the tolerances and the path
+  const WavePlan p = wave_plan(m->KK + 1, m->has_plog, m->has_general, cfg->rtol, 0, true);
+  const int rc = visit_wave_variant<true>(p.n64, p.pl, [&](auto N, auto PL) {
+    return launch_reactors<decltype(N)::value, decltype(PL)::value, true, true>(m, n, dc, io, st);
+  });
   if (rc) return rc;
-  HIP_CHECK(hipGetLastError());
+  CKMI_HIP_CHECK(hipGetLastError());
   return CKMI_OK;
 }
 

@@ -730,7 +730,7 @@ __device__ __forceinline__ double bpermute(int src_lane, double v) {
 //   NewtonMatrixF32S  FP64 Gauss-Jordan, inverse stored in FP32 between factorisations (N VGPRs:
 //                     3 waves per SIMD); the default
 //   NewtonMatrixGJ64  the same inverse kept in FP64 (2N VGPRs: 2 waves per SIMD), for tolerances
-//                     tighter than an FP32-rounded inverse resolves (rtol < 1e-9, ckmi.hip)
+//                     tighter than an FP32-rounded inverse resolves (wave_plan, ckmi_dispatch.hpp)
 // A factorisation in FP32 (tried, with error-weight equilibration) fails on ~6 % of the bench
 // reactors (Newton convergence / error-test failures): the elimination needs FP64, the stored
 // inverse does not.

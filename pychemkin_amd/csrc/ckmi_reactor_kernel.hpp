@@ -8,7 +8,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <type_traits>
 
@@ -16,12 +15,6 @@
 #include "ckmi_reactor.hpp"
 #include "ckmi_run.hpp"
 #include "ckmi_internal.hpp"
-
-#define CKMI_RK_HIP_CHECK(x)                                                                                  \
-  do {                                                                                                        \
-    hipError_t _e = (x);                                                                                      \
-    if (_e != hipSuccess) return ckmi::set_error(CKMI_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 namespace {
 using namespace ckmi;
@@ -104,6 +97,10 @@ __host__ __device__ constexpr int rwaves(bool f64) { return f64 ? 8 : 12; }
 // near equilibrium, at steps of 1e-2 s and more, the FP32-stored inverse of the tracer mechanisms' Newton matrix
 // no longer contracts the iteration; the FP64 one integrates the same reactors, tests/test_gpu_size_variants.py).
 enum { SEL_ALL = 0, SEL_NO_PFR = 1, SEL_PFR = 2, SEL_PFR_RETRY = 3 };
+// sel of the FP64-inverse launch of a WavePlan (ckmi_dispatch.hpp)
+constexpr int f64_sel(int takes) {
+  return takes == F64_TAKES_ALL ? SEL_ALL : (takes == F64_TAKES_PFR ? SEL_PFR : SEL_PFR_RETRY);
+}
 // PSR: the open well-stirred reactor (problem 5, ckmi_psr_run) instead of the closed ones: every reactor of
 // the launch is a PSR, io is a PsrIO, the wave's slice ends with one more [VL] vector (the inlet mass
 // fractions), and the run ends at the first steady state.  A compile-time flag of three FP64-inverse
@@ -1030,55 +1027,34 @@ size_t reactor_lds_bytes(const ckmi_mech* m) {
 }
 // Grid = (CUs x resident workgroups per CU), capped by the batch; J workspace = one
 // column-major N x 64 matrix per wave slot, allocated stream-ordered (~55 MB for GRI-3.0).
-// Per-launch copy of the run configuration: it lives in the launch's stream-ordered workspace,
-// so launches with different configurations on one mechanism handle (other streams, other host
-// threads) never share it.  The host staging copy is released by a host function enqueued
-// behind the copy, i.e. only once the stream has consumed it.
-int stage_cfg(const DevCfg& dc, DevCfg* dst, hipStream_t stream) {
-  auto* hc = new DevCfg(dc);
-  const hipError_t e = hipMemcpyAsync(dst, hc, sizeof(DevCfg), hipMemcpyHostToDevice, stream);
-  if (e != hipSuccess) {
-    delete hc;
-    return ckmi::set_error(CKMI_ERR_HIP, std::string("cfg copy: ") + hipGetErrorString(e));
-  }
-  CKMI_RK_HIP_CHECK(hipLaunchHostFunc(stream, [](void* p) { delete static_cast<DevCfg*>(p); }, hc));
-  return CKMI_OK;
-}
-
 template <int N, bool PL = false, bool F64 = false, bool PSR = false>
 int launch_reactors(const ckmi_mech* m, int n, const DevCfg& dc, const std::conditional_t<PSR, PsrIO, ReactorIO>& io,
                     hipStream_t stream, int sel = SEL_ALL) {
-  if (!F64 && sel != SEL_NO_PFR) return ckmi::set_error(CKMI_ERR_ARG, "internal: FP32-inverse reactor launch must skip plug flow");
+  if (!F64 && sel != SEL_NO_PFR) return set_error(CKMI_ERR_ARG, "internal: FP32-inverse reactor launch must skip plug flow");
   constexpr int RWAVES = rwaves(F64);
   // open reactors: one more [VL] vector per wave (the inlet mass fractions)
   const size_t lds = reactor_lds_bytes<N, F64>(m) + (PSR ? (size_t)RWAVES * 8 * VL : 0);
-  static thread_local std::map<int, int> max_lds_set;
-  if (lds > 64 * 1024 && max_lds_set[m->device] < (int)lds) {
-    CKMI_RK_HIP_CHECK(hipFuncSetAttribute((const void*)reactor_kernel<N, PL, F64, PSR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    max_lds_set[m->device] = (int)lds;
-  }
+  if (int rc = raise_lds_limit(m->device, (const void*)reactor_kernel<N, PL, F64, PSR>, lds)) return rc;
   int ncu = 0, per_cu = 0;
-  CKMI_RK_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, m->device));
-  CKMI_RK_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reactor_kernel<N, PL, F64, PSR>, RWAVES * WAVE, lds));
-  if (per_cu < 1) return ckmi::set_error(CKMI_ERR_SIZE, "reactor kernel does not fit on a CU (LDS " + std::to_string(lds) + " B)");
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, m->device));
+  CKMI_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reactor_kernel<N, PL, F64, PSR>, RWAVES * WAVE, lds));
+  if (per_cu < 1) return set_error(CKMI_ERR_SIZE, "reactor kernel does not fit on a CU (LDS " + std::to_string(lds) + " B)");
   const int want = (n + RWAVES - 1) / RWAVES;
   const int grid = std::max(1, std::min(ncu * per_cu, want));
   // the wave's parked Jacobian is FP32 (N x 64 floats per wave slot)
-  const size_t jbytes = ((size_t)grid * RWAVES * N * WAVE * sizeof(float) + 255) & ~(size_t)255;
-  const size_t cbytes = (sizeof(DevCfg) + 255) & ~(size_t)255;
-  void* ws = nullptr;
-  CKMI_RK_HIP_CHECK(hipMallocAsync(&ws, jbytes + cbytes + 256, stream));
-  DevCfg* dcfg = (DevCfg*)((char*)ws + jbytes);
-  int* queue = (int*)((char*)ws + jbytes + cbytes);
-  int rc = stage_cfg(dc, dcfg, stream);
-  if (rc == CKMI_OK) {
-    CKMI_RK_HIP_CHECK(hipMemsetAsync(queue, 0, sizeof(int), stream));
-    hipLaunchKernelGGL((reactor_kernel<N, PL, F64, PSR>), dim3(grid), dim3(RWAVES * WAVE), lds, stream, m->img, dcfg, n, sel,
-                       queue, (double*)ws, io);
-    CKMI_RK_HIP_CHECK(hipGetLastError());
-  }
-  CKMI_RK_HIP_CHECK(hipFreeAsync(ws, stream));
-  return rc;
+  const size_t jbytes = StreamWorkspace::aligned((size_t)grid * RWAVES * N * WAVE * sizeof(float));
+  const size_t cbytes = StreamWorkspace::aligned(sizeof(DevCfg));
+  StreamWorkspace ws(stream);
+  if (int rc = ws.alloc(jbytes + cbytes + 256)) return rc;
+  double* jws = ws.take<double>(jbytes);
+  DevCfg* dcfg = ws.take<DevCfg>(cbytes);
+  int* queue = ws.take<int>(256);
+  if (int rc = stage_cfg(dc, dcfg, stream)) return rc;
+  CKMI_HIP_CHECK(hipMemsetAsync(queue, 0, sizeof(int), stream));
+  hipLaunchKernelGGL((reactor_kernel<N, PL, F64, PSR>), dim3(grid), dim3(RWAVES * WAVE), lds, stream, m->img, dcfg, n, sel,
+                     queue, jws, io);
+  CKMI_HIP_CHECK(hipGetLastError());
+  return CKMI_OK;
 }
 
 // ---------------------------------------------------------------- RHS / Jacobian probe (diagnostic)
@@ -1205,22 +1181,19 @@ int launch_rhs_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO&
   const size_t lds = (size_t)m->img.bytes + align16(8 * ncol * LDJ) + slice_vec_bytes(m->G) +
                      align16((int)sizeof(RunCtx)) + (PSR ? 8 * VL : 0);
   int lds_max = 0;
-  CKMI_RK_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, m->device));
   if (lds > (size_t)lds_max)
-    return ckmi::set_error(CKMI_ERR_SIZE, "mechanism image + probe work space exceed the LDS of a CU");
-  const void* fn = (const void*)rhs_probe_kernel<PL, PF, PSR>;
-  if (lds > 64 * 1024) CKMI_RK_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const size_t cbytes = (sizeof(DevCfg) + 255) & ~(size_t)255;
-  void* ws = nullptr;
-  CKMI_RK_HIP_CHECK(hipMallocAsync(&ws, cbytes, stream));
-  int rc = stage_cfg(dc, (DevCfg*)ws, stream);
-  if (rc == CKMI_OK) {
-    hipLaunchKernelGGL((rhs_probe_kernel<PL, PF, PSR>), dim3(std::min(n, PROBE_GRID_MAX)), dim3(WAVE), lds, stream,
-                       m->img, (const DevCfg*)ws, n, sel, ncol, io);
-    CKMI_RK_HIP_CHECK(hipGetLastError());
-  }
-  CKMI_RK_HIP_CHECK(hipFreeAsync(ws, stream));
-  return rc;
+    return set_error(CKMI_ERR_SIZE, "mechanism image + probe work space exceed the LDS of a CU");
+  if (int rc = raise_lds_limit(m->device, (const void*)rhs_probe_kernel<PL, PF, PSR>, lds)) return rc;
+  const size_t cbytes = StreamWorkspace::aligned(sizeof(DevCfg));
+  StreamWorkspace ws(stream);
+  if (int rc = ws.alloc(cbytes)) return rc;
+  DevCfg* dcfg = ws.take<DevCfg>(cbytes);
+  if (int rc = stage_cfg(dc, dcfg, stream)) return rc;
+  hipLaunchKernelGGL((rhs_probe_kernel<PL, PF, PSR>), dim3(std::min(n, PROBE_GRID_MAX)), dim3(WAVE), lds, stream,
+                     m->img, dcfg, n, sel, ncol, io);
+  CKMI_HIP_CHECK(hipGetLastError());
+  return CKMI_OK;
 }
 
 }  // namespace

@@ -83,6 +83,80 @@ WAVE_TABLE = {"subset31": (32, (32, False)), "subset32": (33, (54, False)), "pla
               "plain_t10": (64, (64, False)), "plog_t1": (55, (64, True)), "plog_t10": (64, (64, True))}
 
 
+# ---------------------------------------------------------------------- the chooser itself
+# ckmi_reactor_variant (include/ckmi.h) reads wave_plan / big_plan of csrc/ckmi_dispatch.hpp, the functions
+# every launcher calls.  out: [1 wave | 2 workgroup, N of the FP32-inverse launch or 0 | NB, N of the FP64-inverse
+# launch, PL, 0 all | 1 plug flow and engines | 2 those and the FP32 failures]
+CKMI_OK, CKMI_ERR_UNSUPPORTED = 0, 4   # include/ckmi.h
+# the PSR rows (nvar, plog) -> reactor_kernel<N, PL, true, true>
+PSR_TABLE = {(64, False): (64, False), (54, False): (54, False), (54, True): (64, True)}
+
+
+def _variant(nvar, plog, general, rtol, path, psr):
+    import ctypes as ct
+
+    from pychemkin_amd import _native
+
+    out = (ct.c_int32 * 5)(*[-1] * 5)
+    rc = _native.lib().ckmi_reactor_variant(nvar, int(plog), int(general), rtol, path, int(psr), out)
+    return rc, tuple(out)
+
+
+def test_chooser_agrees_with_the_restatement_and_the_rules():
+    """Every input of the chooser: the kernel family, N / NB and PL against mechanism_variants (written before the
+    chooser existed and not edited for it), the FP64 rule, the FP64 launch's N and the retry flag against the rules
+    as ckmi_dispatch.hpp states them, written out here."""
+    ncase = 0
+    for nvar in range(2, 194):
+        for plog in (False, True):
+            for general in (False, True):
+                for rtol in (1e-6, 1e-9, 1e-10):
+                    for path in range(4):
+                        for psr in (False, True):
+                            rc, out = _variant(nvar, plog, general, rtol, path, psr)
+                            what = (nvar, plog, general, rtol, path, psr)
+                            ncase += 1
+                            if nvar > (64 if psr else 192):
+                                assert rc == CKMI_ERR_UNSUPPORTED, what
+                                continue
+                            assert rc == CKMI_OK, what
+                            if not psr and (nvar > 64 or path == 1):
+                                nb, pl = mv.big_variant(nvar, plog)
+                                assert out == (2, nb, 0, int(pl), 0), what
+                                continue
+                            n, pl = mv.wave_variant(nvar, plog)
+                            # FP64 inverse alone: forced (2), or not forced off (3) and tight or general orders;
+                            # an open reactor always
+                            f64 = psr or path == 2 or (path != 3 and (rtol < 1e-9 or general))
+                            n64 = 64 if (plog or nvar > 54) else 54      # no 32-wide FP64-inverse variant
+                            if f64:
+                                assert out == (1, 0, n64, int(pl), 0), what
+                            else:
+                                retry = path == 0 and n64 == 64          # automatic path, 64-wide variants only
+                                assert out == (1, n, n64, int(pl), 2 if retry else 1), what
+    assert ncase == 192 * 2 * 2 * 3 * 4 * 2
+
+
+def test_chooser_gives_the_tables_variants():
+    """WAVE_CASES on the paths they force, BIG_CASES and the PSR rows of DESIGN.md section 10 get the variant the
+    table names."""
+    for name, (nvar, (n, pl), paths) in mv.WAVE_CASES.items():
+        for path in paths:
+            rc, out = _variant(nvar, pl, False, mv.WAVE_RUN["rtol"], path, False)
+            assert rc == CKMI_OK and out[0] == 1 and out[3] == int(pl), (name, path)
+            if path == 2:
+                assert out[1:3] == (0, n), (name, path)           # one launch, FP64 inverse
+            else:
+                assert out[1] == n and out[4] == (2 if path == 0 else 1), (name, path)
+    for (nvar, plog), nb in BIG_TABLE.items():
+        for path in (0, 1):
+            assert _variant(nvar, plog, False, mv.BIG_RUN["rtol"], path, False) == (CKMI_OK, (2, nb, 0, int(plog), 0))
+    assert _variant(54, False, False, 1e-8, 1, False) == (CKMI_OK, (2, 4, 0, 0, 0))   # GRI-3.0 forced: <4, false>
+    for (nvar, plog), (n, pl) in PSR_TABLE.items():
+        for path in range(4):
+            assert _variant(nvar, plog, False, 1e-6, path, True) == (CKMI_OK, (1, 0, n, int(pl), 0))
+
+
 @pytest.mark.parametrize("name", list(mv.WAVE_CASES))
 def test_wave_reactor_inputs(name):
     nvar, variant, _ = mv.WAVE_CASES[name]
