@@ -210,12 +210,14 @@ struct Rxn {
 // PLOG = false compiles the mechanism-without-PLOG kernels exactly as before PLOG existed (the
 // PLOG branch costs 2-4 % of rate throughput in register allocation even when never taken).
 // PRE: the Arrhenius parameters come in as pA (lnA, beta, Ea), loaded ahead by the caller.
+// cs: if given, receives the eight slot concentrations gathered for pf and pr (reactant slots 0..3, product
+// slots 0..3; 1.0 for slots 2, 3 of a strip without them), so that a Jacobian pass does not gather them again.
 template <bool PLOG = false, bool PRE = false>
 __device__ __forceinline__ Rxn eval_rxn_img(const MechView& V, int i, uint32_t inf, uint32_t rs, uint32_t ps,
                                             uint32_t nuw, double T, double lnT, double invT, double lnPRT, double P,
                                             const double* C, const double* gRT, const double* hRT, const double* Mg,
                                             bool need_h, int pslot = -1, double plnf = 0.0, double gfac = 1.0,
-                                            const double* pA = nullptr) {
+                                            const double* pA = nullptr, double* cs = nullptr) {
   constexpr double INV_LN10 = 0.43429448190325176;
   const int type = rx_type(inf);
   // pslot / plnf: per-reactor A-factor perturbation (brute-force sensitivity).  Behind a test of pslot
@@ -357,10 +359,17 @@ __device__ __forceinline__ Rxn eval_rxn_img(const MechView& V, int i, uint32_t i
       }
     }
   }
-  double pf = C[r0] * C[r1], pr = C[p0] * C[p1];
+  const double cr0 = C[r0], cr1 = C[r1], cp0 = C[p0], cp1 = C[p1];
+  double cr2 = 1.0, cr3 = 1.0, cp2 = 1.0, cp3 = 1.0;  // the dummy species' C, as a skipped gather would read it
+  double pf = cr0 * cr1, pr = cp0 * cp1;
   if (s23) {
-    pf *= C[r2] * C[r3];
-    pr *= C[p2] * C[p3];
+    cr2 = C[r2], cr3 = C[r3], cp2 = C[p2], cp3 = C[p3];
+    pf *= cr2 * cr3;
+    pr *= cp2 * cp3;
+  }
+  if (cs) {  // (a compile-time test once inlined: callers without cs compile to what they were)
+    cs[0] = cr0, cs[1] = cr1, cs[2] = cr2, cs[3] = cr3;
+    cs[4] = cp0, cs[5] = cp1, cs[6] = cp2, cs[7] = cp3;
   }
   Rxn e;
   e.kf = kf * gfac;  // GFAC scales forward and reverse rates alike

@@ -47,6 +47,8 @@ struct WaveLds {
   __device__ __forceinline__ double* Mg() const { return lds_at<double>(base + 48 * VL); }
 };
 constexpr int LDJ = WAVE + 1;  // leading dimension of the shared J scratch (odd: conflict-free columns)
+// byte offset, from the scratch, of the lock of a shared J scratch of ncol columns (16-byte aligned)
+__host__ __device__ constexpr int jlock_offset(int ncol) { return (8 * ncol * LDJ + 15) & ~15; }
 
 struct RunCtx {
   int conp, energy;
@@ -177,21 +179,20 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 // J[1+k][1+j] += (+/-) dq W_k / W_j for every (unit-coefficient) slot k of one reaction
-// (column-major shared scratch Jsh[col * LDJ + row]).
-__device__ __forceinline__ void jac_scatter(const MechView& V, int oJ, int nr, int np, uint32_t rs, uint32_t ps,
-                                            int j, double dq) {
+// (column-major shared scratch Jsh[col * LDJ + row]).  The caller gathers the slots' row weights W_k
+// (wr: reactants, wp: products) and the column's 1 / W_j (rwj) once per strip: between the atomics the
+// compiler merges no loads, and a reaction's up to 8 calls would each read the same up to 8 weights again.
+// s23: slots 2, 3 in use anywhere in the wave (wave-uniform); without them their atomics are skipped as a
+// scalar branch, not lane by lane.
+__device__ __forceinline__ void jac_scatter(int oJ, int nr, int np, uint32_t rs, uint32_t ps, const double (&wr)[4],
+                                            const double (&wp)[4], bool s23, int j, double rwj, double dq) {
   double* col = lds_at<double>(oJ) + (1 + j) * LDJ + 1;
-  const double dqw = dq * V.rwt()[j];
+  const double dqw = dq * rwj;
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    if (u < nr) {
-      const int k = sp_of(rs, u);
-      atomicAdd(&col[k], -dqw * V.wt()[k]);
-    }
-    if (u < np) {
-      const int k = sp_of(ps, u);
-      atomicAdd(&col[k], dqw * V.wt()[k]);
-    }
+    if (u >= 2 && !s23) break;
+    if (u < nr) atomicAdd(&col[sp_of(rs, u)], -dqw * wr[u]);
+    if (u < np) atomicAdd(&col[sp_of(ps, u)], dqw * wp[u]);
   }
 }
 
@@ -238,8 +239,7 @@ __device__ __noinline__ void gen_jac_terms(const MechView& V, const RunCtx& R, i
 }
 
 // Right-hand side f(t, y) (one component per lane, lane 0 = T) and, if with_j, the
-// approximate analytic Jacobian into the workgroup's shared J scratch (column-major, the
-// caller holds its lock).  Same formulation as oracle/ckoracle.c reactor_rhs().  with_j is a
+// approximate analytic Jacobian into the J scratch (column-major; its lock: LOCK below).  Same formulation as oracle/ckoracle.c reactor_rhs().  with_j is a
 // run-time (wave-uniform) flag that selects one of two passes over the reactions -- the plain one
 // (wdot only) or the Jacobian one, which scatters wdot next to dwdot/dT and dq/dC from the same q --
 // so the integrator has a single RHS call site, the register peak is that of one pass, and the f a
@@ -251,7 +251,14 @@ __device__ __noinline__ void gen_jac_terms(const MechView& V, const RunCtx& R, i
 // with 1 / tau = R.G (given) or R.G / rho (volume given), Yin the inlet mass fractions (wave's LDS slice).
 // The Jacobian gains the -1 / tau diagonal, the temperature row's inflow part and, with the volume given,
 // the derivatives of 1 / tau = mdot / (rho V): (1 / tau) / T by T and (1 / tau) Wbar / W_j by Y_j.
-template <bool PL, bool PF, bool PSR = false>
+// LOCK: the J scratch is shared by the waves of a workgroup (reactor_kernel) and a with_j call takes its
+//   lock itself -- the int behind the scratch's ncol columns, 0 = free -- at the first touch of the scratch:
+//   after the prologue (thermo, third-body sums), which works on the wave's own slice only.  The caller
+//   releases it once it has copied J out.  From the acquisition to the end of the call there is no return and
+//   no break out of the call: the strip loops' `continue` only moves to the next strip, so every with_j call
+//   that takes the lock hands it, held, to its caller.  Without LOCK (the probe, the engine heat release
+//   kernel: one wave per scratch) the scratch is the caller's own and is zeroed in the prologue.
+template <bool PL, bool PF, bool PSR = false, bool LOCK = false>
 __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R, double t, double yl,
                                               const WaveLds& L, int oJ, int ncol, bool with_j,
                                               const double* Yin
@@ -328,7 +335,7 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
   }
   const double Ctot = rho * sumYW;  // = sum_k C_k, without a second reduction
   double* Jsh = lds_at<double>(oJ);
-  if (with_j) {
+  if (!LOCK && with_j) {
     for (int idx = lane; idx < ncol * LDJ; idx += WAVE) Jsh[idx] = 0.0;
   }
   wave_lds_sync();
@@ -360,6 +367,21 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
   }
   wave_lds_sync();
   SUB_PHASE(0);
+  if constexpr (LOCK) {
+    if (with_j) {
+      // exclusive use of the workgroup's J scratch from here until the caller has copied it out
+      int* lock = lds_at<int>(oJ + jlock_offset(ncol));
+      for (;;) {
+        int got = 0;
+        if (wave_lane() == 0) got = atomicCAS(lock, 0, 1) == 0;
+        if (uni(bcast(got, 0))) break;
+        __builtin_amdgcn_s_sleep(4);
+      }
+      wave_lds_sync();
+      for (int idx = wave_lane(); idx < ncol * LDJ; idx += WAVE) Jsh[idx] = 0.0;
+      wave_lds_sync();  // the zeros precede every lane's atomics (LDS operations of a wave complete in order)
+    }
+  }
   const int IIp = V.IIp;
   // A-factor perturbation: the slot is read once per call, and only the strip that holds it (a wave-uniform
   // test) passes it on; the others carry no compare, select or LDS read for it (eval_rxn_img)
@@ -421,8 +443,10 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
       }
       if (nr + np == 0) continue;
       const uint32_t rs = V.rsp()[i], ps = V.psp()[i], nuw = V.nu()[i];
+      // cs: the eight slot concentrations, from the gathers eval_rxn_img makes for pf and pr
+      double cs[8];
       const Rxn e = eval_rxn_img<PL>(V, i, inf, rs, ps, nuw, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), true,
-                                 psl, R.plnf, R.gfac);
+                                 psl, R.plnf, R.gfac, nullptr, cs);
       const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
       double dqdT = e.mfac * (e.kf * e.dlkf * e.pf - e.kr * e.dlkr * e.pr);
       if (conp) {
@@ -445,22 +469,38 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
       }
       // dq/dC_j for every reactant slot (forward) and product slot (reverse): the product of
       // the other three slots' concentrations (a species in two slots contributes twice)
-      const int r0 = sp_of(rs, 0), r1 = sp_of(rs, 1), r2 = sp_of(rs, 2), r3 = sp_of(rs, 3);
-      const int p0 = sp_of(ps, 0), p1 = sp_of(ps, 1), p2 = sp_of(ps, 2), p3 = sp_of(ps, 3);
+      // (slots 2, 3 as columns are skipped as a wave where no lane has them, like the rows in jac_scatter)
+      // every slot's row weight W_k, gathered once per strip (unused slots hold the dummy species, whose table
+      // entry exists; slots 2, 3 only where some lane of the wave has them).  Here, behind the wdot / dwdT
+      // atomics, and with each column's 1 / W_j read where its scatter begins: this form takes 244 B of
+      // scratch per lane in the configs[2] kernel; with the weights ahead of those atomics it takes 256 B and
+      // measured 3.3 % slower, with the eight 1 / W_j gathered beside them 268 B and 0.6 % slower, and the
+      // FP64-inverse variants start to spill ("Jacobian events")
+      double wr[4], wp[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const bool on = u < 2 || s23;
+        wr[u] = on ? V.wt()[sp_of(rs, u)] : 0.0;
+        wp[u] = on ? V.wt()[sp_of(ps, u)] : 0.0;
+      }
       const double kf = e.mfac * e.kf, kr = -e.mfac * e.kr;
       if (e.kf != 0.0) {
-        const double c0 = C[r0], c1 = C[r1], c2 = C[r2], c3 = C[r3];
+        const double c0 = cs[0], c1 = cs[1], c2 = cs[2], c3 = cs[3];
         const double d[4] = {c1 * c2 * c3, c0 * c2 * c3, c0 * c1 * c3, c0 * c1 * c2};
 #pragma unroll
-        for (int sl = 0; sl < 4; ++sl)
-          if (sl < nr) jac_scatter(V, oJ, nr, np, rs, ps, sp_of(rs, sl), kf * d[sl]);
+        for (int sl = 0; sl < 4; ++sl) {
+          if (sl >= 2 && !s23) break;
+          if (sl < nr) jac_scatter(oJ, nr, np, rs, ps, wr, wp, s23, sp_of(rs, sl), V.rwt()[sp_of(rs, sl)], kf * d[sl]);
+        }
       }
       if (e.kr != 0.0) {
-        const double c0 = C[p0], c1 = C[p1], c2 = C[p2], c3 = C[p3];
+        const double c0 = cs[4], c1 = cs[5], c2 = cs[6], c3 = cs[7];
         const double d[4] = {c1 * c2 * c3, c0 * c2 * c3, c0 * c1 * c3, c0 * c1 * c2};
 #pragma unroll
-        for (int sl = 0; sl < 4; ++sl)
-          if (sl < np) jac_scatter(V, oJ, nr, np, rs, ps, sp_of(ps, sl), kr * d[sl]);
+        for (int sl = 0; sl < 4; ++sl) {
+          if (sl >= 2 && !s23) break;
+          if (sl < np) jac_scatter(oJ, nr, np, rs, ps, wr, wp, s23, sp_of(ps, sl), V.rwt()[sp_of(ps, sl)], kr * d[sl]);
+        }
       }
     }
   }

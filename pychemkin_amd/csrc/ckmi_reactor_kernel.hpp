@@ -126,7 +126,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
   constexpr bool PF = F64;
   const ckmi_reactor_cfg* __restrict__ cfg = &dcfg->c;
   const int oJ = img.bytes;
-  const int olock = oJ + align16(8 * N * LDJ);
+  const int olock = oJ + jlock_offset(N);  // where reactor_rhs<..., LOCK> looks for it
   if (threadIdx.x == 0) *lds_at<int>(olock) = 0;
   stage_image(0, img);
   const MechView V = make_view(0, img);
@@ -532,14 +532,10 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
             const int jbad = S.nst == 0 || S.nst >= S.nstlj + MSBJ || (c.convfail == CF_BAD_J && dgamma < DGMAX) ||
                              c.convfail == CF_OTHER;
             if (jbad) {
-              // exclusive use of the workgroup's J scratch until it is copied out
-              for (;;) {
-                int got = 0;
-                if (lane == 0) got = atomicCAS(lds_at<int>(olock), 0, 1) == 0;
-                if (uni(bcast(got, 0))) break;
-                __builtin_amdgcn_s_sleep(4);
-              }
-              wave_lds_sync();
+              // the with_j call takes the lock of the workgroup's J scratch itself, behind its prologue
+              // (reactor_rhs<..., LOCK>), and returns holding it; ST_NLS_J -- the state this request sets, which
+              // nothing between here and there changes: the call has no early exit, and the loop around the
+              // switch dispatches on st alone -- copies J out and releases it, unconditionally
               REQUEST_F(S.tn, b.y, ST_NLS_J);
               with_j = true;
               break;
@@ -1002,7 +998,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
 #endif
 #ifdef CKMI_PHASE_TIMERS
     unsigned long long sub[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    fe = reactor_rhs<PL, PF, PSR>(V, R, t_e, y_e, L, oJ, N, with_j, Yin, sub);
+    fe = reactor_rhs<PL, PF, PSR, true>(V, R, t_e, y_e, L, oJ, N, with_j, Yin, sub);
     ph[with_j ? PH_JAC : PH_RHS] += __builtin_amdgcn_s_memtime() - t0;
     if (!with_j) {
       ph[5] += sub[0];
@@ -1014,7 +1010,8 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
       }
     }
 #else
-    fe = reactor_rhs<PL, PF, PSR>(V, R, t_e, y_e, L, oJ, N, with_j, Yin);
+    // (LOCK: a with_j call takes the lock at olock = oJ + jlock_offset(N) and returns holding it)
+    fe = reactor_rhs<PL, PF, PSR, true>(V, R, t_e, y_e, L, oJ, N, with_j, Yin);
 #endif
   }
 #undef REQUEST_F
