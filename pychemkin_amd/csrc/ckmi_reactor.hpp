@@ -979,17 +979,28 @@ __device__ __forceinline__ double wrms_lane(double v, double ewt, int n) {
   return sqrt(wave_sum(x * x) / n);
 }
 
+// The order loops below have bdf_predict's form: every zn[j] (and S.l[j], S.tau[i]) is read unconditionally
+// into locals, the run-time order selects, and every entry is stored back (one beyond q with the value it
+// had): independent LDS reads and one wait, not a chain of one-access blocks behind scalar branches.  Each
+// expression keeps the shape of the loop it replaces (same operations, same contraction).  They carry no
+// device intrinsic and compile for the host too (tests/step_control_host.cpp checks them word for word
+// against the branch forms).
 template <class BB, class SS>
-__device__ __forceinline__ void bdf_rescale(BB& b, SS& S) {
-  double factor = S.eta;
+__host__ __device__ __forceinline__ void bdf_rescale(BB& b, SS& S) {
+  const int q = S.q;
+  const double eta = S.eta;
+  double z[QMAX + 1];
+#pragma unroll
+  for (int j = 1; j <= QMAX; ++j) z[j] = b.zn[j];
+  double factor = eta;
 #pragma unroll
   for (int j = 1; j <= QMAX; ++j) {
-    if (j <= S.q) {
-      b.zn[j] *= factor;
-      factor *= S.eta;
-    }
+    z[j] = (j <= q) ? z[j] * factor : z[j];
+    factor = (j <= q) ? factor * eta : factor;
   }
-  S.h = S.hscale * S.eta;
+#pragma unroll
+  for (int j = 1; j <= QMAX; ++j) b.zn[j] = z[j];
+  S.h = S.hscale * eta;
   S.hscale = S.h;
 }
 
@@ -1104,66 +1115,112 @@ __device__ __forceinline__ void bdf_set(BB& b, SS& S) {
 }
 
 
+// the recursion for l[] on locals (wave-uniform branches on q, as bdf_set's), the history by selects
 template <class BB, class SS>
-__device__ __forceinline__ void bdf_adjust_order(BB& b, SS& S, int deltaq) {
+__host__ __device__ __forceinline__ void bdf_adjust_order(BB& b, SS& S, int deltaq) {
   const int q = S.q;
+  const double hscale = S.hscale;
+  double tau[QMAX + 1];
 #pragma unroll
-  for (int i = 0; i <= QMAX; ++i) S.l[i] = 0.0;
-  S.l[2] = 1.0;
+  for (int i = 1; i <= QMAX; ++i) tau[i] = S.tau[i];
+  double z[QMAX + 1];
+#pragma unroll
+  for (int j = 0; j <= QMAX; ++j) z[j] = b.zn[j];
+  double l[QMAX + 1];
+#pragma unroll
+  for (int i = 0; i <= QMAX; ++i) l[i] = 0.0;
+  l[2] = 1.0;
   if (deltaq == 1) {
-    double alpha1 = 1.0, prod = 1.0, xiold = 1.0, alpha0 = -1.0, hsum = S.hscale;
+    double alpha1 = 1.0, prod = 1.0, xiold = 1.0, alpha0 = -1.0, hsum = hscale;
 #pragma unroll
     for (int j = 1; j < QMAX; ++j) {
       if (j < q) {
-        hsum += S.tau[j + 1];
-        const double xi = hsum / S.hscale;
+        hsum += tau[j + 1];
+        const double xi = hsum / hscale;
         prod *= xi;
         alpha0 -= 1.0 / (j + 1);
         alpha1 += 1.0 / xi;
 #pragma unroll
         for (int i = QMAX; i >= 2; --i)
-          if (i <= j + 2) S.l[i] = S.l[i] * xiold + S.l[i - 1];
+          if (i <= j + 2) l[i] = l[i] * xiold + l[i - 1];
         xiold = xi;
       }
     }
     const double A1 = (-alpha0 - alpha1) / prod;
-    const double znL = A1 * b.zn[QMAX];
+    const double znL = A1 * z[QMAX];
 #pragma unroll
-    for (int j = 2; j <= QMAX; ++j)
-      if (j <= q) b.zn[j] += S.l[j] * znL;
+    for (int j = 2; j <= QMAX; ++j) z[j] = (j <= q) ? z[j] + l[j] * znL : z[j];
 #pragma unroll
-    for (int j = 1; j <= QMAX; ++j)
-      if (j == q + 1) b.zn[j] = znL;
+    for (int j = 1; j <= QMAX; ++j) z[j] = (j == q + 1) ? znL : z[j];
   } else {
     double hsum = 0.0;
 #pragma unroll
     for (int j = 1; j <= QMAX; ++j) {
       if (j <= q - 2) {
-        hsum += S.tau[j];
-        const double xi = hsum / S.hscale;
+        hsum += tau[j];
+        const double xi = hsum / hscale;
 #pragma unroll
         for (int i = QMAX; i >= 2; --i)
-          if (i <= j + 2) S.l[i] = S.l[i] * xi + S.l[i - 1];
+          if (i <= j + 2) l[i] = l[i] * xi + l[i - 1];
       }
     }
     double znq = 0.0;
 #pragma unroll
-    for (int j = 0; j <= QMAX; ++j)
-      if (j == q) znq = b.zn[j];
+    for (int j = 0; j <= QMAX; ++j) znq = (j == q) ? z[j] : znq;
 #pragma unroll
-    for (int j = 2; j <= QMAX; ++j)
-      if (j < q) b.zn[j] -= S.l[j] * znq;
+    for (int j = 2; j <= QMAX; ++j) z[j] = (j < q) ? z[j] - l[j] * znq : z[j];
   }
+#pragma unroll
+  for (int i = 0; i <= QMAX; ++i) S.l[i] = l[i];
+#pragma unroll
+  for (int j = 1; j <= QMAX; ++j) b.zn[j] = z[j];
 }
 
 template <class BB, class SS>
-__device__ __forceinline__ double dky0_lane(const BB& b, const SS& S, double t) {
+__host__ __device__ __forceinline__ double dky0_lane(const BB& b, const SS& S, double t) {
+  const int q = S.q;
   const double sc = (t - S.tn) / S.h;
+  double z[QMAX + 1];
+#pragma unroll
+  for (int j = 0; j <= QMAX; ++j) z[j] = b.zn[j];
   double v = 0.0;
 #pragma unroll
-  for (int j = QMAX; j >= 0; --j)
-    if (j <= S.q) v = b.zn[j] + sc * v;
+  for (int j = QMAX; j >= 0; --j) v = (j <= q) ? z[j] + sc * v : v;
   return v;
+}
+
+// the accepted step into the history: zn[j] += l[j] * acor for j <= q, and acor parked in zn[QMAX] where
+// the next step will select the order (park)
+template <class BB, class SS>
+__host__ __device__ __forceinline__ void bdf_correct_history(BB& b, const SS& S, int q, bool park) {
+  const double acor = b.acor;
+  double z[QMAX + 1], l[QMAX + 1];
+#pragma unroll
+  for (int j = 0; j <= QMAX; ++j) {
+    z[j] = b.zn[j];
+    l[j] = S.l[j];
+  }
+#pragma unroll
+  for (int j = 0; j <= QMAX; ++j) z[j] = (j <= q) ? z[j] + l[j] * acor : z[j];
+  z[QMAX] = park ? acor : z[QMAX];
+#pragma unroll
+  for (int j = 0; j <= QMAX; ++j) b.zn[j] = z[j];
+}
+
+// the step sizes of the accepted steps, shifted by one (nst counts the accepted step); returns tau[2]
+template <class SS>
+__host__ __device__ __forceinline__ double bdf_tau_shift(SS& S, int q, int nst, double h) {
+  double t[QMAX + 1];
+#pragma unroll
+  for (int i = 1; i <= QMAX; ++i) t[i] = S.tau[i];
+  double u[QMAX + 1];
+#pragma unroll
+  for (int i = QMAX; i >= 2; --i) u[i] = (i <= q) ? t[i - 1] : t[i];
+  u[2] = (q == 1 && nst > 1) ? t[1] : u[2];
+  u[1] = h;
+#pragma unroll
+  for (int i = 1; i <= QMAX; ++i) S.tau[i] = u[i];
+  return u[2];
 }
 
 }  // namespace ckmi

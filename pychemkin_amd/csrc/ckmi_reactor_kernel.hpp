@@ -183,7 +183,7 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
     b.zn[0] = act ? (Y_) : 0.0;                                        \
     _Pragma("unroll") for (int j_ = 1; j_ <= QMAX; ++j_) b.zn[j_] = 0.0; \
     b.ewt = act ? 1.0 / (S.rtol * fabs(b.zn[0]) + S.atol) : 0.0;       \
-    c.st_tout = (TOUT_);                                               \
+    c.tc = c.st_tout = (TOUT_); /* the step loop's stop point */      \
     R.tsel = 0.5 * (S.tn + c.st_tout);                                 \
     c.st_h0 = (H0_);                                                   \
     REQUEST_F(S.tn, b.zn[0], ST_START_F);                              \
@@ -358,6 +358,9 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           c.icrit = 0;
           c.first = 1;
           c.max_steps = cfg->max_steps > 0 ? cfg->max_steps : 200000;
+          c.flags = (dcfg->ncrit > 0 ? SF_CRIT : 0) | (cfg->ign_stop ? SF_IGN_STOP : 0) | (io.nsave > 0 ? SF_SAVE : 0) |
+                    (io.n_adap ? SF_ADAP : 0) | (cfg->asteps > 0 ? SF_ASTEPS : 0) | (cfg->avar >= 0 ? SF_AVAR : 0) |
+                    (dcfg->npe << SF_NPE_SHIFT);
 #ifdef CKMI_PHASE_TIMERS
 #pragma unroll
           for (int k = 0; k < 8; ++k) ph[k] = 0;
@@ -482,33 +485,37 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           break;
         }
         case ST_STEP_BEGIN: {
-          if (!(S.tn < c.tend * (1.0 - 1e-15))) {
+          // one batch of independent reads (c.tc is crit_time(dcfg, c.tend, c.icrit): set where icrit is, in
+          // START_BEGIN, not asked of dcfg per step)
+          const double tn = S.tn, tend = c.tend, tc = c.tc, h = S.h, rtol = S.rtol, atol = S.atol, z0 = b.zn[0];
+          double hprime = S.hprime;
+          const int nst = S.nst, q = S.q, qprime = S.qprime;
+          if (!(tn < tend * (1.0 - 1e-15))) {
             st = ST_FINISH;
             break;
           }
-
-          c.tc = crit_time(dcfg, c.tend, c.icrit);
-          if (S.tn + S.hprime > c.tc) {
-            const double hp = c.tc - S.tn;
-            S.eta = hp / S.h;
-            if (S.nst > 0) {
+          if (tn + hprime > tc) {
+            const double hp = tc - tn;
+            S.eta = hp / h;
+            if (nst > 0) {
+              hprime = hp;
               S.hprime = hp;
             } else {
               bdf_rescale(b, S);
               S.hprime = S.h;
             }
           }
-          b.ewt = act ? 1.0 / (S.rtol * fabs(b.zn[0]) + S.atol) : 0.0;
-          c.told = S.tn;
-          c.saved_t = S.tn;
+          b.ewt = act ? 1.0 / (rtol * fabs(z0) + atol) : 0.0;
+          c.told = tn;
+          c.saved_t = tn;
           c.ncf = c.nef = 0;
           c.nflag = NF_FIRST;
-          if (S.nst > 0 && S.hprime != S.h) {
-            if (S.qprime != S.q) {
-              bdf_adjust_order(b, S, S.qprime - S.q);
-              S.q = S.qprime;
-              S.L = S.q + 1;
-              S.qwait = S.L;
+          if (nst > 0 && hprime != h) {  // (at nst == 0 the clip above leaves hprime == h)
+            if (qprime != q) {
+              bdf_adjust_order(b, S, qprime - q);
+              S.q = qprime;
+              S.L = qprime + 1;
+              S.qwait = qprime + 1;
             }
             bdf_rescale(b, S);
           }
@@ -518,8 +525,12 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
         case ST_STEP_ATTEMPT: {
           bdf_predict(b, S);
           bdf_set(b, S);
-          c.convfail = (c.nflag == NF_FIRST || c.nflag == NF_ERR_FAIL) ? CF_NONE : CF_OTHER;
-          c.call_setup = (c.nflag != NF_FIRST) || S.nst == 0 || S.nst >= S.nstlp + MSBP || fabs(S.gamrat - 1.0) > DGMAX;
+          {  // every input read at once; the tests combine without short-circuit branches
+            const int nflag = c.nflag, nst = S.nst, nstlp = S.nstlp;
+            const double gamrat = S.gamrat;
+            c.convfail = (nflag == NF_FIRST || nflag == NF_ERR_FAIL) ? CF_NONE : CF_OTHER;
+            c.call_setup = (nflag != NF_FIRST) | (nst == 0) | (nst >= nstlp + MSBP) | (fabs(gamrat - 1.0) > DGMAX);
+          }
           st = ST_NLS_ATTEMPT;
           break;
         }
@@ -528,9 +539,10 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           // a stale Jacobian (oracle nls_setup's jbad: none of its inputs depends on f) is decided here, so
           // that f and J of the point come from ONE evaluation, its reactions visited once
           if (c.call_setup) {
+            const int nst = S.nst, nstlj = S.nstlj, convfail = c.convfail;
             const double dgamma = fabs(S.gamma / S.gammap - 1.0);
-            const int jbad = S.nst == 0 || S.nst >= S.nstlj + MSBJ || (c.convfail == CF_BAD_J && dgamma < DGMAX) ||
-                             c.convfail == CF_OTHER;
+            const int jbad = (nst == 0) | (nst >= nstlj + MSBJ) | ((convfail == CF_BAD_J) & (dgamma < DGMAX)) |
+                             (convfail == CF_OTHER);
             if (jbad) {
               // the with_j call takes the lock of the workgroup's J scratch itself, behind its prologue
               // (reactor_rhs<..., LOCK>), and returns holding it; ST_NLS_J -- the state this request sets, which
@@ -608,15 +620,17 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
 #ifdef CKMI_PHASE_TIMERS
           ph[PH_SOLVE] += __builtin_amdgcn_s_memtime() - t0;
 #endif
+          // one batch of independent reads behind the solve (nothing of it lives across the solve)
+          const double gamrat = S.gamrat, crate0 = S.crate, tq4 = S.tq[4], delp = c.delp, z0 = b.zn[0];
+          const int nneg = S.nneg, mm = c.mm;
           S.nni++;
-          if (S.gamrat != 1.0) x *= 2.0 / (1.0 + S.gamrat);
+          if (gamrat != 1.0) x *= 2.0 / (1.0 + gamrat);
           if (!act) x = 0.0;
           // the iteration's norms in one fused reduction (oracle nls: the same quantities): the correction
           // (del), the accumulated correction (acnrm), NNEG's negative part and acnrm after NNEG's clipping
-          const double z0 = b.zn[0];
           b.acor += x;
           b.y = z0 + b.acor;
-          const bool neg = S.nneg && act && lane >= 1 && b.y < 0.0;
+          const bool neg = nneg && act && lane >= 1 && b.y < 0.0;
           double nv[4];
           {
             const double xe = x * b.ewt, ae = b.acor * b.ewt, ne = neg ? b.y * b.ewt : 0.0;
@@ -628,11 +642,15 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           }
           wave_sum_multi<4>(nv, lane);
           const double del = sqrt(nv[0] / n);
-          if (c.mm > 0) S.crate = fmax(CRDOWN * S.crate, del / c.delp);
-          const double dcon = del * fmin(1.0, S.crate) / S.tq[4];
+          double crate = crate0;
+          if (mm > 0) {
+            crate = fmax(CRDOWN * crate0, del / delp);
+            S.crate = crate;
+          }
+          const double dcon = del * fmin(1.0, crate) / tq4;
           if (dcon <= 1.0) {
             bool negfail = false, negfix = false;
-            if (S.nneg && nv[2] > 0.0) {
+            if (nneg && nv[2] > 0.0) {
               if (sqrt(nv[2] / n) > NNEG_TOL) {
                 negfail = true;
               } else {
@@ -648,13 +666,13 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
               st = ST_NLS_FAIL;
               break;
             }
-            S.acnrm = (c.mm == 0 && !negfix) ? del : sqrt((negfix ? nv[3] : nv[1]) / n);
+            S.acnrm = (mm == 0 && !negfix) ? del : sqrt((negfix ? nv[3] : nv[1]) / n);
             S.jcur = 0;
             st = ST_ERRTEST;
             break;
           }
-          c.mm++;
-          if (c.mm == MAXCOR || (c.mm >= 2 && del > RDIV * c.delp)) {
+          c.mm = mm + 1;
+          if (mm + 1 == MAXCOR || (mm + 1 >= 2 && del > RDIV * delp)) {
             c.failed = 1;
             st = ST_NLS_FAIL;
             break;
@@ -742,96 +760,99 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           break;
         }
         case ST_STEP_COMPLETE: {
-          const double dsm = c.dsm;
-          S.nst++;
+          // one batch of independent reads; the decisions run on locals, the changed fields are stored once
+          const double dsm = c.dsm, h = S.h, etamax = S.etamax, hmax_inv = S.hmax_inv, tq5 = S.tq[5];
+          double saved_tq5 = S.saved_tq5;
+          const int q = S.q, Lq = S.L, nst = S.nst + 1, fl = c.flags;
+          int qwait = S.qwait;
+          S.nst = nst;
           c.nst++;
-          S.hu = S.h;
-#pragma unroll
-          for (int i = QMAX; i >= 2; --i)
-            if (i <= S.q) S.tau[i] = S.tau[i - 1];
-          if (S.q == 1 && S.nst > 1) S.tau[2] = S.tau[1];
-          S.tau[1] = S.h;
+          S.hu = h;
+          const double tau2 = bdf_tau_shift(S, q, nst, h);
           // the q - 1 and q + 1 error norms of a step that selects the next order (qwait reaches 0 below), from
           // the corrector before the element projection (oracle bdf_step), in one fused 2-value reduction
           double ddn = 0.0, dup = 0.0;
-          if (S.etamax != 1.0 && S.qwait == 1) {
-            const bool qm = S.q > 1, qp = S.q != QMAX && S.saved_tq5 != 0.0;
+          if (etamax != 1.0 && qwait == 1) {
+            const bool qm = q > 1, qp = q != QMAX && saved_tq5 != 0.0;
+            const double tq1 = S.tq[1], tq3 = S.tq[3];
             double cquot = 0.0;
             if (qp) {
-              const double hr = S.h / S.tau[2];
+              const double hr = h / tau2;
               double hrL = hr;
-              for (int j = 1; j < S.L; ++j) hrL *= hr;
-              cquot = (S.tq[5] / S.saved_tq5) * hrL;
+              for (int j = 1; j < Lq; ++j) hrL *= hr;
+              cquot = (tq5 / saved_tq5) * hrL;
             }
             double ov[2];
             {
-              double znq = 0.0, lq = 0.0;
+              // zn[q] and l[q]: every entry read, the order selects (scalars, not arrays: a select chain over
+              // a local array folds into a dynamically indexed stack slot)
+              double znq = 0.0, lq = 0.0, znQ = 0.0;
 #pragma unroll
-              for (int j = 0; j <= QMAX; ++j)
-                if (j == S.q) {
-                  znq = b.zn[j];
-                  lq = S.l[j];
-                }
+              for (int j = 0; j <= QMAX; ++j) {
+                const double zj = b.zn[j], lj = S.l[j];
+                znq = (j == q) ? zj : znq;
+                lq = (j == q) ? lj : lq;
+                if (j == QMAX) znQ = zj;
+              }
               const double a = (act && qm) ? (znq + lq * b.acor) * b.ewt : 0.0;
-              const double t = (act && qp) ? (b.acor - cquot * b.zn[QMAX]) * b.ewt : 0.0;
+              const double t = (act && qp) ? (b.acor - cquot * znQ) * b.ewt : 0.0;
               ov[0] = a * a;
               ov[1] = t * t;
             }
             wave_sum_multi<2>(ov, lane);
-            ddn = sqrt(ov[0] / n) * S.tq[1];
-            dup = sqrt(ov[1] / n) * S.tq[3];
+            ddn = sqrt(ov[0] / n) * tq1;
+            dup = sqrt(ov[1] / n) * tq3;
           }
           // element conservation held to PROJ_TOL rtol (oracle elem_project), before the history update
-          if (dcfg->npe) elem_project_wave(V, dcfg->npe, c.eb0, S.rtol, b.zn[0], b.acor, lane, L.ek());
-#pragma unroll
-          for (int j = 0; j <= QMAX; ++j)
-            if (j <= S.q) b.zn[j] += S.l[j] * b.acor;
-          S.qwait--;
-          if (S.qwait == 1 && S.q != QMAX) {
-            b.zn[QMAX] = b.acor;
-            S.saved_tq5 = S.tq[5];
-          }
-          if (S.etamax == 1.0) {
-            if (S.qwait < 2) S.qwait = 2;
-            S.qprime = S.q;
-            S.hprime = S.h;
-            S.eta = 1.0;
+          if (const int npe = fl >> SF_NPE_SHIFT) elem_project_wave(V, npe, c.eb0, S.rtol, b.zn[0], b.acor, lane, L.ek());
+          qwait--;
+          const bool park = qwait == 1 && q != QMAX;
+          bdf_correct_history(b, S, q, park);
+          if (park) saved_tq5 = tq5;
+          double eta, hprime;
+          int qprime = q;
+          if (etamax == 1.0) {
+            if (qwait < 2) qwait = 2;
+            hprime = h;
+            eta = 1.0;
           } else {
-            const double etaq = 1.0 / (eta_root(BIAS2 * dsm, S.L) + ADDON);
-            if (S.qwait != 0) {
-              S.eta = etaq;
-              S.qprime = S.q;
+            const double etaq = 1.0 / (eta_root(BIAS2 * dsm, Lq) + ADDON);
+            if (qwait != 0) {
+              eta = etaq;
             } else {
-              S.qwait = 2;
+              qwait = 2;
               double etaqm1 = 0.0, etaqp1 = 0.0;
-              if (S.q > 1) etaqm1 = 1.0 / (eta_root(BIAS1 * ddn, S.q) + ADDON);
-              if (S.q != QMAX && S.saved_tq5 != 0.0) etaqp1 = 1.0 / (eta_root(BIAS3 * dup, S.L + 1) + ADDON);
+              if (q > 1) etaqm1 = 1.0 / (eta_root(BIAS1 * ddn, q) + ADDON);
+              if (q != QMAX && saved_tq5 != 0.0) etaqp1 = 1.0 / (eta_root(BIAS3 * dup, Lq + 1) + ADDON);
               const double etam = fmax(etaqm1, fmax(etaq, etaqp1));
               if (etam < THRESH) {
-                S.eta = 1.0;
-                S.qprime = S.q;
+                eta = 1.0;
               } else if (etam == etaq) {
-                S.eta = etaq;
-                S.qprime = S.q;
+                eta = etaq;
               } else if (etam == etaqm1) {
-                S.eta = etaqm1;
-                S.qprime = S.q - 1;
+                eta = etaqm1;
+                qprime = q - 1;
               } else {
-                S.eta = etaqp1;
-                S.qprime = S.q + 1;
+                eta = etaqp1;
+                qprime = q + 1;
                 b.zn[QMAX] = b.acor;
               }
             }
-            if (S.eta < THRESH) {
-              S.eta = 1.0;
-              S.hprime = S.h;
+            if (eta < THRESH) {
+              eta = 1.0;
+              hprime = h;
             } else {
-              S.eta = fmin(S.eta, S.etamax);
-              S.eta /= fmax(1.0, fabs(S.h) * S.hmax_inv * S.eta);
-              S.hprime = S.h * S.eta;
+              eta = fmin(eta, etamax);
+              eta /= fmax(1.0, fabs(h) * hmax_inv * eta);
+              hprime = h * eta;
             }
           }
-          S.etamax = (S.nst <= SMALL_NST) ? ETAMX2 : ETAMX3;
+          S.qwait = qwait;
+          S.saved_tq5 = saved_tq5;
+          S.qprime = qprime;
+          S.hprime = hprime;
+          S.eta = eta;
+          S.etamax = (nst <= SMALL_NST) ? ETAMX2 : ETAMX3;
           {  // runaway guard on the accepted state: a mass fraction far below 0, or T off the thermo range
              // (energy runs); it ends the reactor through ST_STEP_END's failure exit
             // (one ballot, not a max reduction: only "any lane beyond the guard" matters)
@@ -851,22 +872,26 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
           break;
         }
         case ST_STEP_END: {
-          if (c.rc != 0) {
-            c.status = c.rc;
+          // one batch of independent reads for the common path
+          const int rc = c.rc, fl = c.flags, gmode = g.mode, nst = c.nst, max_steps = c.max_steps;
+          const double tn = S.tn;
+          if (rc != 0) {
+            c.status = rc;
             st = ST_FINISH;
             break;
           }
-          const double tn = S.tn;
-          while (c.isave < io.nsave && io.t_save[c.isave] <= tn) {
-            const double ys = dky0_lane(b, S, io.t_save[c.isave]);
-            if (act) io.y_save[((size_t)c.r * io.nsave + c.isave) * n + lane] = ys;
-            c.isave++;
+          if (fl & SF_SAVE) {
+            while (c.isave < io.nsave && io.t_save[c.isave] <= tn) {
+              const double ys = dky0_lane(b, S, io.t_save[c.isave]);
+              if (act) io.y_save[((size_t)c.r * io.nsave + c.isave) * n + lane] = ys;
+              c.isave++;
+            }
           }
-          if (g.mode == 1) {
+          if (gmode == 1) {
             ign_peak_update(g, tn, bcast(b.zn[1], 0) / S.h);
-          } else if (g.mode == 4) {
+          } else if (gmode == 4) {
             ign_peak_update(g, tn, bcast(b.zn[0], g.comp));
-          } else if ((g.mode == 2 || g.mode == 3) && !g.found && bcast(b.zn[0], 0) >= g.thresh) {
+          } else if ((gmode == 2 || gmode == 3) && !g.found && bcast(b.zn[0], 0) >= g.thresh) {
             double lo = c.told, hi = tn;
             for (int it = 0; it < 60; ++it) {
               const double mid = 0.5 * (lo + hi);
@@ -877,23 +902,23 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
             g.tau = hi;
           }
           st = ST_STEP_BEGIN;
-          if (cfg->ign_stop) {
-            if ((g.mode == 2 || g.mode == 3) && g.found) {
+          if (fl & SF_IGN_STOP) {
+            if ((gmode == 2 || gmode == 3) && g.found) {
               c.stopped = 1;
               st = ST_FINISH;
               break;
             }
-            if (g.mode == 1 && g.have_next && g.vlast < 0.1 * g.best && bcast(b.zn[0], 0) > c.T0 + 200.0) {
+            if (gmode == 1 && g.have_next && g.vlast < 0.1 * g.best && bcast(b.zn[0], 0) > c.T0 + 200.0) {
               c.stopped = 1;
               st = ST_FINISH;
               break;
             }
           }
           bool adap = false;
-          if (io.n_adap && c.nadap < io.max_adap) {
+          if ((fl & SF_ADAP) && c.nadap < io.max_adap) {
             // ADAP: extra solution points every ASTEPS steps, or when AVAR moved by AVALUE
-            if (cfg->asteps > 0 && c.nst % cfg->asteps == 0) adap = true;
-            if (cfg->avar >= 0 && cfg->avalue > 0.0) {
+            if ((fl & SF_ASTEPS) && nst % cfg->asteps == 0) adap = true;
+            if ((fl & SF_AVAR) && cfg->avalue > 0.0) {
               const double v = bcast(b.zn[0], cfg->avar);
               if (fabs(v - c.avar_last) >= cfg->avalue) adap = true;
             }
@@ -903,14 +928,14 @@ __global__ __launch_bounds__(rwaves(F64)* WAVE) void reactor_kernel(MechImage im
             if (lane == 0) io.t_adap[a] = tn;
             if (act) io.y_adap[a * n + lane] = b.zn[0];
             c.nadap++;
-            if (cfg->avar >= 0) c.avar_last = bcast(b.zn[0], cfg->avar);
+            if (fl & SF_AVAR) c.avar_last = bcast(b.zn[0], cfg->avar);
           }
-          if (c.nst >= c.max_steps) {
+          if (nst >= max_steps) {
             c.status = CKMI_RUN_MAXSTEPS;
             st = ST_FINISH;
             break;
           }
-          if (tn >= c.tc * (1.0 - 1e-15) && c.icrit < c.ncrit - 1) {
+          if ((fl & SF_CRIT) && tn >= c.tc * (1.0 - 1e-15) && c.icrit < c.ncrit - 1) {
             c.icrit++;
             START_BEGIN(tn, b.zn[0], crit_time(dcfg, c.tend, c.icrit), 0.0);
           }

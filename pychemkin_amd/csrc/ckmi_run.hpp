@@ -119,12 +119,26 @@ constexpr int PROBE_GRID_MAX = 64;  // workgroups of a probe launch (states beyo
 struct Ctl {
   int r, first, nflag, convfail, call_setup, failed, mm, ncf, nef, rc, isave, icrit, ncrit, status, nst, stopped;
   int is_count, max_steps, nadap;
+  int flags;  // SF_*: what a step asks of the run configuration, packed once per reactor (in the ints' padding)
   double avar_last;
   double delp, saved_t, told, dsm, tc, tend, hmax, T0;
   double yguard, tguard_lo, tguard_hi;  // runaway guard (DevCfg), copied per reactor
   double st_h0, st_tout, st_h, is_hg, is_hub, is_hlb, is_t0;
   double eb0[PROJ_MMAX];  // the reactor's initial element contents (element projection)
   double tdh;             // h dT/dt of the accepted state (workgroup kernel: from the step's fused reduction)
+};
+
+static_assert(offsetof(Ctl, avar_last) == 80, "Ctl::flags takes the padding behind the ints: the slice keeps its size");
+// Ctl::flags of the wave-per-reactor kernel: the per-step questions to cfg, dcfg and io, answered at ST_NEXT, so
+// that a step reads one LDS word and goes to global memory only where a flag sends it
+enum {
+  SF_CRIT = 1,       // the run has critical times (profile breakpoints) before t_end
+  SF_IGN_STOP = 2,   // cfg.ign_stop
+  SF_SAVE = 4,       // save points exist (io.nsave > 0)
+  SF_ADAP = 8,       // ADAP output is on (io.n_adap)
+  SF_ASTEPS = 16,    // cfg.asteps > 0
+  SF_AVAR = 32,      // cfg.avar >= 0
+  SF_NPE_SHIFT = 8   // bits 8 and up: dcfg.npe, the elements of the projection (0 = off)
 };
 
 // Per-wave LDS slice: 6 species vectors, third-body sums, integrator scalars, control state,
