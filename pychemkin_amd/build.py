@@ -14,6 +14,7 @@ BIG_HDR = os.path.join(HERE, "csrc", "ckmi_big_matrix.hpp")  # its register-resi
 KIN_SRC = os.path.join(HERE, "csrc", "ckmi_kin.cpp")  # KIN-compatible host shims (include/ckmi_kin.h)
 JIT_SRC = os.path.join(HERE, "csrc", "ckmi_jit.cpp")  # mechanism-specialised ROP kernel generator (hipRTC)
 PARSE_SRC = os.path.join(HERE, "csrc", "ckmi_parse.cpp")  # native Chemkin-II interpreter (KINPreProcess)
+MECH_SRC = os.path.join(HERE, "csrc", "ckmi_mech_host.cpp")  # mechanism image builder (host only, no HIP call)
 TRAN_SRC = os.path.join(HERE, "csrc", "ckmi_transport.hip")  # viscosity fits + species / mixture viscosity
 PSR_SRC = os.path.join(HERE, "csrc", "ckmi_psr.hip")  # steady-state PSRs: the open-reactor kernel instantiations
 EQUIL_SRC = os.path.join(HERE, "csrc", "ckmi_equil.hip")  # batched chemical equilibrium and CJ states
@@ -22,7 +23,7 @@ NET_SRC = os.path.join(HERE, "csrc", "ckmi_network.hip")  # PSR networks: flow b
 TRAN_HDR = os.path.join(HERE, "csrc", "ckmi_transport.hpp")  # the ckmi_transport tables both transport units share
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("ckmi_device.hpp", "ckmi_reactor.hpp", "ckmi_image.hpp",
                                                 "ckmi_run.hpp", "ckmi_internal.hpp", "ckmi_reactor_kernel.hpp",
-                                                "ckmi_dispatch.hpp")] + [
+                                                "ckmi_dispatch.hpp", "ckmi_mech_host.hpp")] + [
     os.path.join(HERE, "..", "include", "ckmi.h"), os.path.join(HERE, "..", "include", "ckmi_kin.h")]
 OUT = os.path.join(HERE, "_lib", "libckmi.so")
 OBJ_DIR = os.path.join(HERE, "_lib", "obj")
@@ -59,7 +60,7 @@ def _stale(target: str, sources) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(OUT, [SRC, LU_SRC, BIG_SRC, KIN_SRC, JIT_SRC, PARSE_SRC, TRAN_SRC, PSR_SRC, EQUIL_SRC, DIFF_SRC, NET_SRC, TRAN_HDR] + DEPS)
+    return _stale(OUT, [SRC, LU_SRC, BIG_SRC, KIN_SRC, JIT_SRC, PARSE_SRC, MECH_SRC, TRAN_SRC, PSR_SRC, EQUIL_SRC, DIFF_SRC, NET_SRC, TRAN_HDR] + DEPS)
 
 
 PROF_OUT = os.path.join(HERE, "_lib", "libckmi_prof.so")  # diagnostic phase-timer build
@@ -77,8 +78,9 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
 
     Separately compiled translation units (the reactor kernel alone takes ~2 min) linked into one
     shared library: ckmi.hip, ckmi_psr.hip, ckmi_network.hip, ckmi_equil.hip, ckmi_lu.hip, ckmi_big.hip, ckmi_transport.hip,
-    ckmi_diffusion.hip and the host-only ckmi_kin.cpp,
-    ckmi_parse.cpp and ckmi_jit.cpp (linked with libhiprtc)."""
+    ckmi_diffusion.hip and the host-only ckmi_kin.cpp, ckmi_parse.cpp, ckmi_mech_host.cpp (the mechanism image
+    builder: no HIP call, so tests/mech_image_host.cpp links it without a device) and ckmi_jit.cpp (linked with
+    libhiprtc)."""
     default = out is None and not prof and not extra
     out = out or (PROF_OUT if prof else OUT)
     if not force and default and not needs_build():
@@ -103,6 +105,11 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
     parse_obj = os.path.join(OBJ_DIR, "ckmi_parse.o")
     if force or _stale(parse_obj, [PARSE_SRC] + DEPS):
         jobs.append((PARSE_SRC, parse_obj, KIN_FLAGS))
+    # (the image builder sizes the dense third-body table by the reactor kernel's LDS slice, which the
+    # phase-timer build enlarges: that build gets an object of its own)
+    mech_obj = os.path.join(OBJ_DIR, "ckmi_mech_host_prof.o" if prof else "ckmi_mech_host.o")
+    if force or _stale(mech_obj, [MECH_SRC] + DEPS):
+        jobs.append((MECH_SRC, mech_obj, KIN_FLAGS + (["-DCKMI_PHASE_TIMERS"] if prof else [])))
     tran_obj = os.path.join(OBJ_DIR, "ckmi_transport.o")
     if force or _stale(tran_obj, [TRAN_SRC, TRAN_HDR] + DEPS):
         jobs.append((TRAN_SRC, tran_obj, LU_FLAGS))
@@ -133,7 +140,7 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False, out: s
         for f in [pool.submit(_compile, s, o, fl, verbose) for s, o, fl in jobs]:
             f.result()
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, main_obj, lu_obj, big_obj, kin_obj, jit_obj,
-           parse_obj, tran_obj, diff_obj, psr_obj, equil_obj, net_obj,
+           parse_obj, mech_obj, tran_obj, diff_obj, psr_obj, equil_obj, net_obj,
            "-L/opt/rocm/lib", "-lhiprtc", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)

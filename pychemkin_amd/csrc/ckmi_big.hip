@@ -495,7 +495,7 @@ __device__ __forceinline__ double rhs_big(const MechView& V, const RunCtx& R, co
     for (int idx = tid; idx < jcb * LDJ; idx += NT) jb[idx] = 0.0;
     __syncthreads();
     const int lo = c0 + wid * cpw, hi = lo + cpw;  // this wave's columns
-    // the unit slots naming this wave's species lo - 1 .. hi - 2 (host-built CSR lists, ckmi.hip build_image),
+    // the unit slots naming this wave's species lo - 1 .. hi - 2 (host-built CSR lists, ckmi_mech_host.cpp pack_image),
     // one per lane: each wave visits only its own slots instead of all 8 IIp of them per column block (3 % on
     // configs[4]; the atomics add into each entry in another order than the all-slot walk did)
     {

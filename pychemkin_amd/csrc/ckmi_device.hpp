@@ -1,7 +1,7 @@
 // ckmi_device.hpp -- device-side building blocks for gfx950 (CDNA4, wave64).
 //
-// Wave utilities (DPP reductions, broadcasts) and the global-memory mechanism tables (MechDev,
-// used by the thread-per-state species-thermo kernel and for the reaction-order map; the rate
+// Wave utilities (DPP reductions, broadcasts) and the global-memory species tables (MechDev, read by the
+// thread-per-state species-thermo kernel, the network's stream mixing and the transport fits; the rate
 // kernels read the LDS image of ckmi_image.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,39 +17,12 @@ constexpr double RU = BOLTZMANN * AVOGADRO;  // erg/mol-K (reference constants.p
 constexpr double PATM = 1.01325e6;           // dyn/cm2  (reference constants.py:28)
 constexpr double LN_PATM_RU = -4.407419774071825;  // ln(PATM / RU): ln(PATM / (RU T)) = LN_PATM_RU - ln T
 
-// Device-resident mechanism tables.  Reactions are re-ordered by type (elementary first,
-// then third-body, then falloff) so that a 64-lane strip is type-uniform; `orig` maps a
-// device slot back to the reference reaction index.  All per-reaction arrays have IIpad
-// entries (pad slots carry nr = np = 0 and produce nothing).
+// Device-resident species tables (built by build_host_mech, uploaded by ckmi_mech_create).
 struct MechDev {
-  int KK, II, IIpad, G;
+  int KK;
   const double* wt;     // [KK]
   const double* rwt;    // [KK] 1/W
   const double* th;     // [17][KK] tlow, tmid, thigh, low a1..a7, high a1..a7 (coefficient-major)
-  const int* flags;     // [IIpad] type | rev<<2 | has_rev<<3 | ftype<<4
-  const int* nrp;       // [IIpad] nr | np<<8
-  const int4* rsp;      // [IIpad]
-  const int4* psp;      // [IIpad]
-  const double* rnu;    // [SLOTS][IIpad]
-  const double* pnu;    // [SLOTS][IIpad]
-  const double* lnA;    // [IIpad]
-  const double* beta;
-  const double* Ea;     // E/R
-  const double* lnA0;   // low-pressure limit
-  const double* beta0;
-  const double* Ea0;
-  const double* fp;     // [5][IIpad] TROE / SRI
-  const double* rlnA;   // explicit REV
-  const double* rbeta;
-  const double* rEa;
-  const double* dnu;    // [IIpad] sum(nu'') - sum(nu')
-  const double* ordf;   // [IIpad] sum(nu')
-  const double* ordr;   // [IIpad] sum(nu'')
-  const int* tb;        // [IIpad] >=0 third-body group, <= -2 collider species -(tb+2), -1 none
-  const int* orig;      // [IIpad] original reaction index, -1 for pad
-  const int* gptr;      // [G+1]
-  const int* gsp;
-  const double* geff;   // efficiency - 1
 };
 
 // ------------------------------------------------------------------ wave utilities

@@ -1,7 +1,8 @@
 // ckmi_image.hpp -- compact mechanism image, staged once per workgroup into LDS.
 //
-// ckmi_mech_create packs every table the rate kernels read into one contiguous byte image
-// (~28 KB for GRI-Mech 3.0).  A kernel workgroup copies it from HBM into LDS with 16-byte
+// build_host_mech (ckmi_mech_host.cpp, host code only) packs every table the rate kernels read into one
+// contiguous byte image (~28 KB for GRI-Mech 3.0) and ckmi_mech_create uploads it; tests/mech_image_host.cpp
+// checks the bytes against the descriptor.  A kernel workgroup copies it from HBM into LDS with 16-byte
 // loads once, and all of its waves (one reactor or one state each) then read rate
 // parameters, stoichiometry and NASA-7 coefficients at LDS latency instead of L2 latency.
 //
@@ -21,8 +22,10 @@
 //   aux       double [naux][13]  lnA0 b0 E0/R, falloff parameters (TROE: a, 1/T***, 1/T*, T**;
 //                                SRI: a, b, 1/c, d, e), REV lnA b E/R, pad (AUXW)
 //   gptr i32 [G+1], gsp i32 [ng], geff double [ng]   third-body efficiency lists (eff - 1)
-//   geffd double [G][KKp]   the same lists dense (eff - 1, 0 for unlisted species)
+//   geffd double [64][17]   the same lists dense and transposed (eff - 1 at [species][group], 0 for unlisted
+//                           species) where KK <= 63, G <= 16 and the LDS holds it; a 2-double stub otherwise
 //   e2t   double [32]       2^(j/32), the table of fexp (E2T_N)
+//   el    u64 [KKp]         element counts for the corrector's element projection, one byte per element
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -120,16 +123,17 @@ __device__ __forceinline__ void stage_image(int base, const MechImage& I) {
 }
 
 // ------------------------------------------------------------------ info / packing helpers
-__device__ __forceinline__ int rx_type(uint32_t inf) { return inf & 3; }
-__device__ __forceinline__ bool rx_rev(uint32_t inf) { return (inf >> 2) & 1; }
-__device__ __forceinline__ bool rx_hasrev(uint32_t inf) { return (inf >> 3) & 1; }
-__device__ __forceinline__ int rx_ftype(uint32_t inf) { return (inf >> 4) & 7; }
-__device__ __forceinline__ int rx_nr(uint32_t inf) { return (inf >> 7) & 7; }
-__device__ __forceinline__ int rx_np(uint32_t inf) { return (inf >> 10) & 7; }
-__device__ __forceinline__ int rx_aux(uint32_t inf) { return inf >> 16; }
-__device__ __forceinline__ int sp_of(uint32_t packed, int u) { return (packed >> (8 * u)) & 0xff; }
-__device__ __forceinline__ int nur_of(uint32_t nu, int u) { return (nu >> (4 * u)) & 0xf; }
-__device__ __forceinline__ int nup_of(uint32_t nu, int u) { return (nu >> (16 + 4 * u)) & 0xf; }
+// (host and device: the image builder and its host test decode with the kernels' own helpers)
+__host__ __device__ __forceinline__ int rx_type(uint32_t inf) { return inf & 3; }
+__host__ __device__ __forceinline__ bool rx_rev(uint32_t inf) { return (inf >> 2) & 1; }
+__host__ __device__ __forceinline__ bool rx_hasrev(uint32_t inf) { return (inf >> 3) & 1; }
+__host__ __device__ __forceinline__ int rx_ftype(uint32_t inf) { return (inf >> 4) & 7; }
+__host__ __device__ __forceinline__ int rx_nr(uint32_t inf) { return (inf >> 7) & 7; }
+__host__ __device__ __forceinline__ int rx_np(uint32_t inf) { return (inf >> 10) & 7; }
+__host__ __device__ __forceinline__ int rx_aux(uint32_t inf) { return inf >> 16; }
+__host__ __device__ __forceinline__ int sp_of(uint32_t packed, int u) { return (packed >> (8 * u)) & 0xff; }
+__host__ __device__ __forceinline__ int nur_of(uint32_t nu, int u) { return (nu >> (4 * u)) & 0xf; }
+__host__ __device__ __forceinline__ int nup_of(uint32_t nu, int u) { return (nu >> (16 + 4 * u)) & 0xf; }
 
 // Info bit 15: on a type-3 slot a Chebyshev rate (aux stream NT, NP, 1/Tmin, 1/Tmax, log10 Pmin,
 // log10 Pmax, a[t][p]) instead of a PLOG table; on a type-0 slot Landau-Teller terms (aux record:

@@ -58,22 +58,6 @@ __device__ __forceinline__ void state_PV(const MechView& M, const RunCtx& R, dou
   }
 }
 
-__host__ __device__ constexpr int slice_vec_bytes(int G) { return align16(8 * (6 * VL + (G > 0 ? G : 1))); }
-#ifdef CKMI_PHASE_TIMERS
-constexpr int PH_SLICE = 8 * 40;  // per-state (0..19) and per-strip (24..29) cycle counters
-#else
-constexpr int PH_SLICE = 0;
-#endif
-__host__ __device__ constexpr int slice_bytes(int G) {
-  return slice_vec_bytes(G) + align16((int)sizeof(BdfS)) + align16((int)sizeof(Ctl)) + align16((int)sizeof(Ign)) +
-         align16((int)sizeof(RunCtx)) + ZN_BYTES + PH_SLICE;
-}
-template <int N>
-__host__ __device__ constexpr int jscratch_bytes() {
-  return align16(8 * N * LDJ) + 16;  // + lock
-}
-
-
 // Persistent reactor kernel: one workgroup of RWAVES waves per CU slot.  The workgroup stages
 // the mechanism image into LDS once; each wave then pulls reactor indices from an HBM work
 // counter until the batch is exhausted (dynamic balancing: step counts differ by 10x across a

@@ -144,6 +144,23 @@ enum {
 // Per-wave LDS slice: 6 species vectors, third-body sums, integrator scalars, control state,
 // ignition monitor.
 __host__ __device__ constexpr int align16(int b) { return (b + 15) & ~15; }
+// LDS sizes of the wave-per-reactor kernel (ckmi_reactor_kernel.hpp): a wave's slice and the shared Jacobian
+// scratch.  Here, not with the kernel, because the image builder (ckmi_mech_host.cpp) sizes its dense
+// third-body table by them.
+__host__ __device__ constexpr int slice_vec_bytes(int G) { return align16(8 * (6 * VL + (G > 0 ? G : 1))); }
+#ifdef CKMI_PHASE_TIMERS
+constexpr int PH_SLICE = 8 * 40;  // per-state (0..19) and per-strip (24..29) cycle counters
+#else
+constexpr int PH_SLICE = 0;
+#endif
+__host__ __device__ constexpr int slice_bytes(int G) {
+  return slice_vec_bytes(G) + align16((int)sizeof(BdfS)) + align16((int)sizeof(Ctl)) + align16((int)sizeof(Ign)) +
+         align16((int)sizeof(RunCtx)) + ZN_BYTES + PH_SLICE;
+}
+template <int N>
+__host__ __device__ constexpr int jscratch_bytes() {
+  return align16(8 * N * LDJ) + 16;  // + lock
+}
 
 // integrator states; the ones marked (f) resume after the RHS requested by their predecessor
 enum {
