@@ -52,6 +52,15 @@ struct MechImage {
   int o_th, o_wt, o_rwt, o_lnA, o_beta, o_Ea, o_rsp, o_psp, o_nu, o_info, o_tb, o_aux, o_gptr, o_gsp, o_geff, o_geffd, o_e2t;
 };
 
+// Layout invariant of the per-slot arrays: lnA, beta, Ea at strides of 8 IIp bytes, then rsp, psp, nu, info,
+// tb at strides of 4 IIp bytes, with no gap.  build_host_mech refuses an image without it.
+inline bool slot_arrays_contiguous(const MechImage& I) {
+  const int sd = 8 * I.IIp, sw = 4 * I.IIp;
+  return I.o_beta == I.o_lnA + sd && I.o_Ea == I.o_lnA + 2 * sd && I.o_rsp == I.o_lnA + 3 * sd &&
+         I.o_psp == I.o_rsp + sw && I.o_nu == I.o_rsp + 2 * sw && I.o_info == I.o_rsp + 3 * sw &&
+         I.o_tb == I.o_rsp + 4 * sw;
+}
+
 // Dynamic LDS of every kernel that stages the image.  Views hold byte OFFSETS into it, not
 // pointers, so that every access is re-derived from this __shared__ symbol and compiles to
 // ds_* instructions even where a view struct is spilled or passed by reference (a generic
@@ -349,10 +358,17 @@ __device__ __forceinline__ Rxn eval_rxn_img(const MechView& V, int i, uint32_t i
       dlkr = (ax[9] + ax[10] * invT) * invT - (rlt ? (ax[3] * t13 + 2.0 * ax[4] * t23) * (1.0 / 3.0) * invT : 0.0);
     } else {
       // unit-coefficient slots: sum_products g - sum_reactants g, dnu = np - nr
-      double gp = gRT[p0] + gRT[p1], gr = gRT[r0] + gRT[r1];
+      // the gathers of one batch are pinned together (an empty volatile asm over all of them): left alone,
+      // the compiler reads the product pair, waits and adds, then reads the reactant pair and waits again --
+      // two dependent LDS round trips for four independent reads.  The sums and their order are unchanged.
+      double gp0 = gRT[p0], gp1 = gRT[p1], gr0 = gRT[r0], gr1 = gRT[r1];
+      asm volatile("" : "+v"(gp0), "+v"(gp1), "+v"(gr0), "+v"(gr1));
+      double gp = gp0 + gp1, gr = gr0 + gr1;
       if (s23) {
-        gp += gRT[p2] + gRT[p3];
-        gr += gRT[r2] + gRT[r3];
+        double gp2 = gRT[p2], gp3 = gRT[p3], gr2 = gRT[r2], gr3 = gRT[r3];
+        asm volatile("" : "+v"(gp2), "+v"(gp3), "+v"(gr2), "+v"(gr3));
+        gp += gp2 + gp3;
+        gr += gr2 + gr3;
       }
       const double dG = gp - gr;
       const int dnu = rx_np(inf) - rx_nr(inf);

@@ -455,6 +455,10 @@ int Builder::pack_image() {
   I.o_nu = put(unu.data(), IIp * 4);
   I.o_info = put(uinfo.data(), IIp * 4);
   I.o_tb = put(tb.data(), IIp * 4);
+  // the per-slot arrays lie back to back at strides of IIp (IIp is a multiple of 64, so the 16-byte alignment
+  // of put() leaves no gap): the reactor kernel's strips address all of them from o_lnA, o_rsp and IIp alone
+  // (strip_head, ckmi_reactor.hpp)
+  if (!slot_arrays_contiguous(I)) return set_error(CKMI_ERR_ARG, "image layout: per-slot arrays not back to back");
   I.o_aux = put(aux.data(), aux.size() * 8);
   I.o_gptr = put(gptr.data(), gptr.size() * 4);
   const int zero = 0;

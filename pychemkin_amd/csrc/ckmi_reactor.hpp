@@ -238,6 +238,60 @@ __device__ __noinline__ void gen_jac_terms(const MechView& V, const RunCtx& R, i
   }
 }
 
+// The records of reaction slot i that every strip of reactor_rhs needs, read as one batch in front of a single
+// wait: info, the species slots, the Arrhenius terms (the pA of eval_rxn_img<PL, true>) and GFAC from the
+// wave's own slice.  Every per-slot array has IIp entries, so a padding slot is a valid read (info = 0, dummy
+// species, zero Arrhenius terms) and the tests of info follow the batch instead of guarding it.  The empty
+// volatile asm over the seven values keeps the compiler from sinking the reads back behind those tests, where
+// they were three dependent LDS round trips (info; slots and lnA; beta and Ea).
+// STRIDE: the addresses come from two lane addresses and the wave-uniform stride IIp: the image builder lays
+// lnA, beta, Ea (8 IIp bytes each) and rsp, psp, nu, info, tb (4 IIp each) back to back and refuses an
+// image that does not (ckmi_mech_host.cpp), so the strips keep two of the view's offsets live, not six, and
+// reload no spilled offset behind the wait.  The reactor kernels take this form (STRIDE = their LOCK); in the
+// probe and the engine heat release kernel it moved 16 B per lane to scratch in the extended plug-flow
+// instantiations, so they address through the view's six offsets (profiles/strip_reads_kernel_resources.txt).
+struct StripHead {
+  uint32_t inf, rs, ps;
+  double pA[3];  // lnA, beta, Ea
+  double gfac;
+};
+template <bool STRIDE>
+__device__ __forceinline__ StripHead strip_head(const MechView& V, const RunCtx& R, int i) {
+  StripHead h;
+  if constexpr (STRIDE) {
+    const int sd = 8 * V.IIp, sw = 4 * V.IIp;
+    const int ad = V.o_lnA + 8 * i, aw = V.o_rsp + 4 * i;
+    h.inf = *lds_at<const uint32_t>(aw + 3 * sw);
+    h.rs = *lds_at<const uint32_t>(aw);
+    h.ps = *lds_at<const uint32_t>(aw + sw);
+    h.pA[0] = *lds_at<const double>(ad);
+    h.pA[1] = *lds_at<const double>(ad + sd);
+    h.pA[2] = *lds_at<const double>(ad + 2 * sd);
+  } else {
+    h.inf = V.info()[i];
+    h.rs = V.rsp()[i];
+    h.ps = V.psp()[i];
+    h.pA[0] = V.lnA()[i];
+    h.pA[1] = V.beta()[i];
+    h.pA[2] = V.Ea()[i];
+  }
+  h.gfac = R.gfac;
+  asm volatile("" : "+v"(h.inf), "+v"(h.rs), "+v"(h.ps), "+v"(h.pA[0]), "+v"(h.pA[1]), "+v"(h.pA[2]), "+v"(h.gfac));
+  return h;
+}
+
+// ln of the A-factor perturbation for the one strip that holds the perturbed slot (psl >= 0, wave-uniform), read
+// behind that test: the pin keeps the compiler from turning the branch into an unconditional read and a select,
+// which would put an LDS round trip of its own between the head batch and the first exp of every strip.
+__device__ __forceinline__ double strip_plnf(const RunCtx& R, int psl) {
+  double plnf = 0.0;
+  if (psl >= 0) {
+    plnf = R.plnf;
+    asm volatile("" : "+v"(plnf));
+  }
+  return plnf;
+}
+
 // Right-hand side f(t, y) (one component per lane, lane 0 = T) and, if with_j, the
 // approximate analytic Jacobian into the J scratch (column-major; its lock: LOCK below).  Same formulation as oracle/ckoracle.c reactor_rhs().  with_j is a
 // run-time (wave-uniform) flag that selects one of two passes over the reactions -- the plain one
@@ -390,7 +444,8 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
     for (int base = 0; base < IIp; base += WAVE) {
       const int i = base + wave_lane();
       const int psl = (unsigned)(pslot - base) < (unsigned)WAVE ? pslot : -1;
-      const uint32_t inf = V.info()[i];
+      const StripHead h = strip_head<LOCK>(V, R, i);
+      const uint32_t inf = h.inf;
       const int nr = rx_nr(inf), np = rx_np(inf);
       if constexpr (PL) {
         if (inf & RX_GEN) {  // FORD / RORD / non-integral coefficients: real nu and orders
@@ -406,9 +461,10 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
         }
       }
       if (nr + np != 0) {
-        const uint32_t rs = V.rsp()[i], ps = V.psp()[i], nuw = V.nu()[i];
-        const Rxn e = eval_rxn_img<PL>(V, i, inf, rs, ps, nuw, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), false,
-                                   psl, R.plnf, R.gfac);
+        // (nu is not read: eval_rxn_img takes the unit slots from rs and ps alone)
+        const uint32_t rs = h.rs, ps = h.ps;
+        const Rxn e = eval_rxn_img<PL, true>(V, i, inf, rs, ps, 0u, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(),
+                                             false, psl, strip_plnf(R, psl), h.gfac, h.pA);
         const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
         const bool s23 = __ballot(nr > 2 || np > 2) != 0;  // wave-uniform: slots 2, 3 in use anywhere
 #pragma unroll
@@ -433,7 +489,8 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
     for (int base = 0; base < IIp; base += WAVE) {
       const int i = base + wave_lane();
       const int psl = (unsigned)(pslot - base) < (unsigned)WAVE ? pslot : -1;
-      const uint32_t inf = V.info()[i];
+      const StripHead h = strip_head<LOCK>(V, R, i);
+      const uint32_t inf = h.inf;
       const int nr = rx_nr(inf), np = rx_np(inf);
       if constexpr (PL) {
         if (inf & RX_GEN) {
@@ -442,11 +499,11 @@ __device__ __forceinline__ double reactor_rhs(const MechView& V, const RunCtx& R
         }
       }
       if (nr + np == 0) continue;
-      const uint32_t rs = V.rsp()[i], ps = V.psp()[i], nuw = V.nu()[i];
       // cs: the eight slot concentrations, from the gathers eval_rxn_img makes for pf and pr
       double cs[8];
-      const Rxn e = eval_rxn_img<PL>(V, i, inf, rs, ps, nuw, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(), true,
-                                 psl, R.plnf, R.gfac, nullptr, cs);
+      const uint32_t rs = h.rs, ps = h.ps;
+      const Rxn e = eval_rxn_img<PL, true>(V, i, inf, rs, ps, 0u, T, lnT, invT, lnPRT, P, C, L.gRT(), L.hRT(), L.Mg(),
+                                           true, psl, strip_plnf(R, psl), h.gfac, h.pA, cs);
       const double q = e.mfac * (e.kf * e.pf - e.kr * e.pr);
       double dqdT = e.mfac * (e.kf * e.dlkf * e.pf - e.kr * e.dlkr * e.pr);
       if (conp) {
