@@ -472,6 +472,28 @@ int ckmi_reactor_rhs_jac(const ckmi_mech* mech, const ckmi_reactor_cfg* cfg, int
                          const double* y, const ckmi_reactor_ext* ext, const ckmi_rhs_psr* psr, double* f, double* J,
                          void* stream);
 
+/* Set-up and solves of the reactor kernels' Newton matrix M = I - gamma J on given matrices.  A diagnostic for
+ * tests: probe kernels of their own call the member functions the integrators call (build_factor / solve of the
+ * wave kernel's NewtonMatrixGJ64 and NewtonMatrixF32S, build / factor / solve of the workgroup kernel's BigMatrixM
+ * and BigMatrix) on one matrix object per wave / workgroup; the integrators do not run, and no mechanism is needed.
+ *   kernel, size, f32_stored          the matrix class: kernel 1 (wave) with size N = 32, 54 or 64 and the FP32-stored
+ *                                     (1) or FP64 (0) inverse, no FP64 form at N = 32; kernel 2 (workgroup) with
+ *                                     size NB = 4..12 (order 16 NB; NB <= 11 the MFMA form) and f32_stored = 0
+ *   nsys, n                           systems and their order, 2 <= n <= N resp. 16 NB
+ *   J [nsys][n][n], gamma [nsys]      J in FP32, row-major: what both kernels park
+ *   J_prev, gamma_prev                optional (both or neither): a set-up made first on the same matrix object and
+ *                                     the same LDS, as a refactorisation or the next reactor of the persistent loop
+ *   nrhs, B [nsys][nrhs][n]           right-hand sides; b_pad: what a wave lane >= n hands to solve(), which zeroes
+ *                                     it (kernel 2 takes 0 only: its solve's contract)
+ *   X [nsys][nrhs][n]                 the solutions
+ *   perm [nsys][n]                    the pivot row of step k
+ *   ok [nsys]                         0 if a pivot's FP32 key was zero (X is then garbage), else 1
+ * CKMI_ERR_ARG: a class that is not compiled, n outside its range, a missing array.  All arrays are device
+ * pointers on the current device. */
+int ckmi_newton_probe(int32_t kernel, int32_t size, int32_t f32_stored, int32_t nsys, int32_t n, const float* J,
+                      const double* gamma, const float* J_prev, const double* gamma_prev, int32_t nrhs, const double* B,
+                      double b_pad, double* X, int32_t* perm, int32_t* ok, void* stream);
+
 /* Reactor kernel selection (diagnostic / testing): 0 = automatic (one wave per reactor for KK + 1 <= 64,
  * its Newton inverse stored in FP32 unless rtol < 1e-9; one 4-wave workgroup per reactor above, up to
  * KK + 1 = 192), 1 = the workgroup-per-reactor kernel for every mechanism (lets tests run both

@@ -136,6 +136,7 @@ PROTOTYPES = {
                                          ct.POINTER(PsrCfg), ct.POINTER(NetworkCfg), ct.POINTER(ct.c_int32)] + [_P] * 20),
     "ckmi_reactor_rhs_jac": (ct.c_int, [_P, ct.POINTER(ReactorCfg), ct.c_int32] + [_P] * 7 +
                              [ct.POINTER(ReactorExt), ct.POINTER(RhsPsr), _P, _P, _P]),
+    "ckmi_newton_probe": (ct.c_int, [ct.c_int32] * 5 + [_P] * 4 + [ct.c_int32, _P, ct.c_double, _P, _P, _P, _P]),
     "ckmi_equil_run": (ct.c_int, [_P, ct.POINTER(EquilCfg), ct.c_int32] + [_P] * 11),
     "ckmi_set_reactor_path": (ct.c_int, [ct.c_int32]),
     "ckmi_big_max_image_bytes": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32]),
@@ -907,6 +908,33 @@ def _lu_check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().ckmi_lu_last_error().decode(errors="replace")
         raise NativeError(f"{what} failed (code {rc}): {msg}")
+
+
+def newton_probe(kernel: int, size: int, f32_stored: bool, J, gamma, B, J_prev=None, gamma_prev=None,
+                 b_pad: float = 0.0, device=0):
+    """Set-up and solves of one Newton-matrix class of the reactor kernels on given matrices (ckmi_newton_probe, a
+    diagnostic).  kernel 1 (wave; size N, FP32-stored or FP64 inverse) or 2 (workgroup; size NB); J [nsys][n][n]
+    (rounded to FP32, what the kernels park), gamma [nsys], B [nsys][nrhs][n]; J_prev / gamma_prev: a set-up made
+    first on the same matrix object.  Returns (X [nsys][nrhs][n], perm [nsys][n], ok [nsys]) as numpy arrays."""
+    dev = torch.device("cuda", device) if isinstance(device, int) else device
+
+    def to(x, dt, shape):
+        return None if x is None else torch.as_tensor(np.ascontiguousarray(x), dtype=dt).reshape(shape).to(dev)
+
+    nsys, n = int(np.shape(J)[0]), int(np.shape(J)[-1])
+    nrhs = int(np.shape(B)[1])
+    Jd, Jp = to(J, torch.float32, (nsys, n, n)), to(J_prev, torch.float32, (nsys, n, n))
+    gd, gp = to(gamma, torch.float64, (nsys,)), to(gamma_prev, torch.float64, (nsys,))
+    Bd = to(B, torch.float64, (nsys, nrhs, n))
+    X = torch.full((nsys, nrhs, n), float("nan"), dtype=torch.float64, device=dev)
+    perm = torch.full((nsys, n), -1, dtype=torch.int32, device=dev)
+    ok = torch.full((nsys,), -1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().ckmi_newton_probe(int(kernel), int(size), int(bool(f32_stored)), nsys, n, _ptr(Jd), _ptr(gd),
+                                       _ptr(Jp), _ptr(gp), nrhs, _ptr(Bd), float(b_pad), _ptr(X), _ptr(perm), _ptr(ok),
+                                       _stream_ptr(dev)), "ckmi_newton_probe")
+        torch.cuda.synchronize(dev)  # a diagnostic call: the inputs may go once it returns
+    return X.cpu().numpy(), perm.cpu().numpy(), ok.cpu().numpy()
 
 
 def lu_factor_batched(A: torch.Tensor):

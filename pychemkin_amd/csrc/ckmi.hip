@@ -838,6 +838,34 @@ int ckmi_reactor_rhs_jac(const ckmi_mech* m, const ckmi_reactor_cfg* cfg, int32_
   return p.pl ? probe(std::true_type{}) : probe(std::false_type{});
 }
 
+int ckmi_newton_probe(int32_t kernel, int32_t size, int32_t f32_stored, int32_t nsys, int32_t n, const float* J,
+                      const double* gamma, const float* J_prev, const double* gamma_prev, int32_t nrhs, const double* B,
+                      double b_pad, double* X, int32_t* perm, int32_t* ok, void* stream) {
+  if (kernel != 1 && kernel != 2) return set_error(CKMI_ERR_ARG, "kernel must be 1 (wave) or 2 (workgroup)");
+  if (nsys < 0 || nrhs < 0) return set_error(CKMI_ERR_ARG, "nsys and nrhs must be >= 0");
+  if (f32_stored != 0 && f32_stored != 1) return set_error(CKMI_ERR_ARG, "f32_stored must be 0 or 1");
+  if (kernel == 2 && (f32_stored || b_pad != 0.0))
+    return set_error(CKMI_ERR_ARG, "the workgroup kernel's matrix has no FP32-stored form, and its solve takes b = 0 beyond n");
+  // the sizes the choosers' visitors compile (a size they do not know is refused below, by the visitor itself)
+  const int nmax = kernel == 1 ? size : 16 * size;
+  if (size < 1 || size > BIG_NMAX || n < 2 || n > nmax) return set_error(CKMI_ERR_ARG, "n must be in [2, the variant's size]");
+  if (nsys > 0 && (!J || !gamma || !perm || !ok || (nrhs > 0 && (!B || !X))))
+    return set_error(CKMI_ERR_ARG, "J, gamma, perm and ok are required, and B and X with nrhs > 0");
+  if ((J_prev == nullptr) != (gamma_prev == nullptr)) return set_error(CKMI_ERR_ARG, "J_prev and gamma_prev go together");
+  const NewtonProbeIO io{nsys, n, nrhs, J, J_prev, gamma, gamma_prev, B, b_pad, X, perm, ok};
+  const hipStream_t st = (hipStream_t)stream;
+  if (kernel == 2) {
+    if (size < 4 || size > 12) return set_error(CKMI_ERR_ARG, "the workgroup kernel is compiled for NB = 4..12");
+    return nsys == 0 ? CKMI_OK : launch_big_newton_probe(size, io, st);
+  }
+  const auto probe = [&](auto F64) {
+    return visit_wave_variant<decltype(F64)::value>(size, false, [&](auto N, auto) {
+      return nsys == 0 ? CKMI_OK : launch_newton_probe<decltype(N)::value, decltype(F64)::value>(io, st);
+    });
+  };
+  return f32_stored ? probe(std::false_type{}) : probe(std::true_type{});
+}
+
 int ckmi_reactor_variant(int32_t nvar, int32_t has_plog, int32_t has_general, double rtol, int32_t path,
                          int32_t open_reactor, int32_t out[5]) {
   if (nvar < 2 || path < 0 || path > 3 || !out) return CKMI_ERR_ARG;

@@ -1548,7 +1548,85 @@ int launch_big_probe_nb(const ckmi_mech* m, int n, int NB, const DevCfg& dc, con
   return CKMI_OK;
 }
 
+// ------------------------------------------------------------------ Newton-matrix probe (diagnostic)
+// ckmi_newton_probe on BigMat<NB>: one workgroup per system makes the calls ST_SETUP and ST_NEWTON_ITER of
+// big_reactor_kernel make -- build(Jg, gamma, tid, n), factor(L, B, tid, wid, lane, n) and solve(b, L, tid, wid,
+// lane) -- in the LDS layout big_layout produces (no mechanism image), on a parked FP32 slot written through
+// jslot(), the index map rhs_big writes through, and on one matrix object that lives across the workgroup's
+// systems, as the persistent loop's does.  Every solve is followed by a barrier: the integrator's next use of the
+// matrix's LDS comes after the iteration's workgroup reductions.  The probe holds its own inlined copy of the
+// member functions: it checks the source the integrator is compiled from, not its machine code.
+template <int NB>
+__global__ __launch_bounds__(NT, 1) void big_newton_probe_kernel(BigLds L, NewtonProbeIO io, float* __restrict__ jws) {
+  const int tid = threadIdx.x;
+  const int wid = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int lane = tid % WAVE;
+  const int n = io.n;
+  float* Jg = jws + (size_t)blockIdx.x * jslot_floats(NB);
+  Blk B;
+  B.ored = L.red;
+  B.phase = 0;
+  BigMat<NB, false> M;
+#ifdef CKMI_PHASE_TIMERS
+  unsigned long long fph[6] = {0, 0, 0, 0, 0, 0};
+#endif
+  for (int s = blockIdx.x; s < io.nsys; s += gridDim.x) {
+    bool ok = true;
+#pragma unroll 1
+    for (int pass = io.Jprev ? 0 : 1; pass < 2; ++pass) {  // pass 0: the set-up before the one that is judged
+      const float* Js = (pass ? io.J : io.Jprev) + (size_t)s * n * n;
+      const double gamma = (pass ? io.gamma : io.gprev)[s];
+      // the slot starts as NaN: a build that reads an entry beyond n as a value shows it
+      for (int idx = tid; idx < jslot_floats(NB); idx += NT) Jg[idx] = __builtin_nanf("");
+      __syncthreads();
+      for (int e = tid; e < n * n; e += NT) Jg[jslot(e / n, e % n, NB)] = Js[e];
+      __syncthreads();  // ST_SETUP's barrier: the slot written by other threads
+      M.build(Jg, gamma, tid, n);
+#ifdef CKMI_PHASE_TIMERS
+      ok = M.factor(L, B, tid, wid, lane, n, fph);
+#else
+      ok = M.factor(L, B, tid, wid, lane, n);
+#endif
+    }
+#pragma unroll 1
+    for (int r = 0; r < io.nrhs; ++r) {
+      const size_t o = ((size_t)s * io.nrhs + r) * n;
+      const double x = M.solve(tid < n ? io.B[o + tid] : 0.0, L, tid, wid, lane);
+      if (tid < n) io.X[o + tid] = x;
+      __syncthreads();
+    }
+    __syncthreads();  // perm of the last step (BigMatrix::step writes it behind the step's barrier)
+    if (tid < n) io.perm[(size_t)s * n + tid] = lds_at<const int>(L.perm)[tid];
+    if (tid == 0) io.ok[s] = ok ? 1 : 0;
+    __syncthreads();  // perm is rewritten by the next system's set-up
+  }
+}
+
+template <int NB>
+int launch_big_newton_probe_nb(const NewtonProbeIO& io, hipStream_t stream) {
+  int dev = 0, lds_max = 0;
+  CKMI_HIP_CHECK(hipGetDevice(&dev));
+  CKMI_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
+  const BigLds L = big_layout(0, 16 * NB, 0, 16 * NB, lds_max);  // KKp = NC: the widest mechanism of the size
+  if (L.jcb < BW || L.bytes > lds_max) return set_error(CKMI_ERR_SIZE, "the workgroup kernel's layout exceeds the LDS of a CU");
+  if (int rc = raise_lds_limit(dev, (const void*)big_newton_probe_kernel<NB>, L.bytes)) return rc;
+  const int grid = std::min(io.nsys, PROBE_GRID_MAX);
+  const size_t jbytes = StreamWorkspace::aligned((size_t)grid * jslot_floats(NB) * sizeof(float));
+  StreamWorkspace ws(stream);
+  if (int rc = ws.alloc(jbytes)) return rc;
+  float* jws = ws.take<float>(jbytes);
+  hipLaunchKernelGGL((big_newton_probe_kernel<NB>), dim3(grid), dim3(NT), L.bytes, stream, L, io, jws);
+  CKMI_HIP_CHECK(hipGetLastError());
+  return CKMI_OK;
+}
+
 }  // namespace
+
+// the matrix sizes visit_big_variant compiles (PL plays no part in the matrix)
+int launch_big_newton_probe(int NB, const NewtonProbeIO& io, hipStream_t stream) {
+  return visit_big_variant(BigPlan{NB, false},
+                           [&](auto NBc, auto) { return launch_big_newton_probe_nb<decltype(NBc)::value>(io, stream); });
+}
 
 // the plan of the mechanism (ckmi_dispatch.hpp); the refusal above BIG_NMAX
 static int big_plan_of(const ckmi_mech* m, BigPlan* p) {

@@ -48,6 +48,7 @@ namespace ckmi {
 struct DevCfg;
 struct ReactorIO;
 struct ProbeIO;
+struct NewtonProbeIO;
 #define CKMI_HIP_CHECK(x)                                                                                        \
   do {                                                                                                           \
     hipError_t e_ = (x);                                                                                         \
@@ -104,4 +105,6 @@ int launch_big_reactors(const ckmi_mech* m, int n, const DevCfg& dc, const React
 // instantiation of the wave kernel's (ckmi_psr.hip)
 int launch_big_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream);
 int launch_psr_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO& io, hipStream_t stream);
+// Newton-matrix probe of ckmi_newton_probe on the workgroup kernel's BigMat<NB> (ckmi_big.hip)
+int launch_big_newton_probe(int NB, const NewtonProbeIO& io, hipStream_t stream);
 }  // namespace ckmi

@@ -1202,4 +1202,55 @@ int launch_rhs_probe(const ckmi_mech* m, int n, const DevCfg& dc, const ProbeIO&
   return CKMI_OK;
 }
 
+// ---------------------------------------------------------------- Newton-matrix probe (diagnostic)
+// ckmi_newton_probe on the wave kernel's matrix forms: one wave per system, in workgroups of the integrator's
+// wave count for the form, makes the calls ST_SETUP and ST_NEWTON_ITER of reactor_kernel make -- build_factor(Jg,
+// WAVE, gamma, n, orow) on a parked FP32 slot in the kernel's Jg[j * WAVE + lane] layout (rows and columns >= n
+// zero) and solve(b, n) -- on one matrix object that lives across the wave's systems, as the persistent loop's
+// does.  The waves' scratch rows are neighbours in LDS.  The probe holds its own inlined copy of the member
+// functions: it checks the source the integrators are compiled from, not their machine code.
+template <int N, bool F64>
+__global__ __launch_bounds__(rwaves(F64) * WAVE) void newton_probe_kernel(NewtonProbeIO io, float* __restrict__ jws) {
+  constexpr int RWAVES = rwaves(F64);
+  const int wid = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int n = io.n;
+  const int orow = wid * align16(8 * N);
+  float* Jg = jws + ((size_t)blockIdx.x * RWAVES + wid) * N * WAVE;
+  std::conditional_t<F64, NewtonMatrixGJ64<N>, NewtonMatrixF32S<N>> M;
+  for (int s = blockIdx.x * RWAVES + wid; s < io.nsys; s += gridDim.x * RWAVES) {
+    bool ok = true;
+#pragma unroll 1
+    for (int pass = io.Jprev ? 0 : 1; pass < 2; ++pass) {  // pass 0: the set-up before the one that is judged
+      const float* Js = (pass ? io.J : io.Jprev) + (size_t)s * n * n;
+      const double gamma = (pass ? io.gamma : io.gprev)[s];
+      for (int j = 0; j < N; ++j)  // lane = row, read back by the same lane
+        Jg[j * WAVE + lane] = (lane < n && j < n) ? Js[(size_t)lane * n + j] : 0.0f;
+      ok = M.build_factor(Jg, WAVE, gamma, n, orow);
+    }
+#pragma unroll 1
+    for (int r = 0; r < io.nrhs; ++r) {
+      const size_t o = ((size_t)s * io.nrhs + r) * n;
+      const double x = M.solve(lane < n ? io.B[o + lane] : io.b_pad, n);
+      if (lane < n) io.X[o + lane] = x;
+    }
+    if (lane < n) io.perm[(size_t)s * n + lane] = M.permv;
+    if (lane == 0) io.ok[s] = ok ? 1 : 0;
+  }
+}
+
+template <int N, bool F64>
+int launch_newton_probe(const NewtonProbeIO& io, hipStream_t stream) {
+  constexpr int RWAVES = rwaves(F64);
+  const int grid = std::min((io.nsys + RWAVES - 1) / RWAVES, PROBE_GRID_MAX);
+  const size_t jbytes = StreamWorkspace::aligned((size_t)grid * RWAVES * N * WAVE * sizeof(float));
+  StreamWorkspace ws(stream);
+  if (int rc = ws.alloc(jbytes)) return rc;
+  float* jws = ws.take<float>(jbytes);
+  hipLaunchKernelGGL((newton_probe_kernel<N, F64>), dim3(grid), dim3(RWAVES * WAVE), RWAVES * align16(8 * N), stream, io,
+                     jws);
+  CKMI_HIP_CHECK(hipGetLastError());
+  return CKMI_OK;
+}
+
 }  // namespace

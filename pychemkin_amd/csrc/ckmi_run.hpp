@@ -115,6 +115,19 @@ struct ProbeIO {
 };
 constexpr int PROBE_GRID_MAX = 64;  // workgroups of a probe launch (states beyond it: grid-stride loop)
 
+// Newton-matrix probe (ckmi_newton_probe, diagnostic): nsys matrices M = I - gamma J of order n, J [nsys][n][n]
+// FP32 row-major as both kernels park it; Jprev / gprev (null: none) a set-up made first on the same matrix
+// object; nrhs right-hand sides B [nsys][nrhs][n]; b_pad what a wave lane >= n hands to solve().  Outputs
+// X [nsys][nrhs][n], perm [nsys][n] (the pivot row of step k) and ok [nsys].
+struct NewtonProbeIO {
+  int nsys, n, nrhs;
+  const float *J, *Jprev;
+  const double *gamma, *gprev, *B;
+  double b_pad;
+  double* X;
+  int *perm, *ok;
+};
+
 // Integrator control state of one wave (wave-uniform scalars, kept in the wave's LDS slice).
 struct Ctl {
   int r, first, nflag, convfail, call_setup, failed, mm, ncf, nef, rc, isave, icrit, ncrit, status, nst, stopped;

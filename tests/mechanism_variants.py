@@ -431,10 +431,16 @@ def rop_reference(KK, plog, n):
 
 
 # ---------------------------------------------------------------------- 3.4 matrices
-def newton_like(rng, nsys, n):
-    """_newton_like of test_gpu_lu.py: I - gamma J with a chemistry-like spread of magnitudes."""
+def newton_like_parts(rng, nsys, n):
+    """(J, gamma) of newton_like: a chemistry-like spread of magnitudes, gamma in 1e-9..1e-5."""
     J = rng.standard_normal((nsys, n, n)) * 10.0 ** rng.uniform(-3, 6, (nsys, n, n))
     gamma = 10.0 ** rng.uniform(-9, -5, (nsys, 1, 1))
+    return J, gamma
+
+
+def newton_like(rng, nsys, n):
+    """_newton_like of test_gpu_lu.py: I - gamma J with a chemistry-like spread of magnitudes."""
+    J, gamma = newton_like_parts(rng, nsys, n)
     return np.eye(n)[None] - gamma * J
 
 
