@@ -862,7 +862,12 @@ struct NewtonMatrixGJ64 {
     const int lane = wave_lane();
     bool pivoted = lane >= N;
     permv = lane;
-    bool ok = true;
+    // the singular test: the smallest of the steps' largest FP32 keys, one wave-uniform running value
+    // (a key is the bit pattern of a non-negative float, so 0 is the smallest).  It starts here, in
+    // every call, and is pinned to an SGPR in its step: left as `if (vmax == 0u) ok = false`, every
+    // step's key is kept to the end of the elimination and the N compares run after the last step
+    // (N = 54: 27 keys in VGPRs across the FP64 elimination, 27 spilled and reloaded one by one).
+    uint32_t vmin = 0xffffffffu;
     // laundered like the lane index: otherwise the 27 row addresses are hoisted out of the
     // reactor loop and held in VGPRs for its whole life
     double2* row = lds_at<double2>(__builtin_amdgcn_readfirstlane(opaque_lane(orow)));
@@ -875,7 +880,11 @@ struct NewtonMatrixGJ64 {
     uint32_t vmax = wave_max_u32(v0);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      if (vmax == 0u) ok = false;
+      {
+        const uint32_t u = __builtin_amdgcn_readfirstlane(vmax);
+        vmin = u < vmin ? u : vmin;
+        asm volatile("" : "+s"(vmin));
+      }
       const uint64_t mask = __ballot(!pivoted && v0 == vmax);
       const int p = uni(mask ? (int)__ffsll((unsigned long long)mask) - 1 : 0);
       const bool me = lane == p;
@@ -896,6 +905,8 @@ struct NewtonMatrixGJ64 {
       const double piv = bcast(a[k], p);
       const double rp = rcp_nr(piv);
       if (me) pivoted = true;
+      // (left to the compiler, which runs the N selects after the last step, p_k waiting in SGPRs: pinned in
+      // its step with an empty asm the tail loses 210 instructions and nothing measurable)
       if (lane == k) permv = p;
       // row p becomes row p / piv; every other row i loses (a_i[k] / piv) x row p.  One FMA
       // form for both: g = (piv - 1) / piv on the pivot lane gives a_p - g a_p = a_p / piv.
@@ -928,7 +939,7 @@ struct NewtonMatrixGJ64 {
       }
       a[k] = ak;
     }
-    return ok;
+    return vmin != 0u;
   }
 
   template <typename TJ>
